@@ -11,10 +11,19 @@ per-pod merge (+ RCCL all-gather across node shards when N > 1), and the
 greedy commit with capacity update; the placements and integer scores are
 copied back to the host.  The reference-mode vote scorer (scheduler.go:248-394
 on one fresh 10k-node snapshot per pod, 48 GB) is timed too and reported under
-"reference_mode".
+"reference_mode" of a --full run.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run does what the headline figure needs and no more: it generates the
+workload, warms up, times the K steps, writes the last timed step's results
+with --dump-outputs, and prints the result line.  --full adds every other
+leg: the per-stage device times, the kernel rooflines with their in-run PMC
+traffic and the vendor GEMM reference, the reference-mode vote scorer, the CPU
+baselines with their oracle checks, the other BASELINE configs and the host
+leg.  --only, --c4 and the --no-* switches select among the legs of a --full
+run.
 
 `--gpus N > 1` without a launcher (no WORLD_SIZE in the environment) starts
 the N rank processes itself (launch_ranks: RANK / LOCAL_RANK / WORLD_SIZE and
@@ -47,6 +56,13 @@ def parse():
     ap.add_argument("--pods", type=int, default=100000)
     ap.add_argument("--dtype", default="i8", choices=["i8", "bf16"])
     ap.add_argument("--peers", type=int, default=8)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline's timed steps: per-stage times, "
+                         "rooflines and PMC traffic, reference mode, CPU baselines and oracle "
+                         "checks, the other configs, the host leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (node.npy: the placements, "
+                         "score.npy: the integer scores, float64) into DIR")
     ap.add_argument("--no-reference-mode", action="store_true")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget-s", type=float, default=20.0)
@@ -79,7 +95,33 @@ def parse():
                          "what the in-run PMC passes profile)")
     ap.add_argument("--no-pmc", action="store_true",
                     help="skip the in-run rocprofv3 PMC passes (roofline.traffic then null)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full and (args.only is not None or args.c4):
+        ap.error("--only and --c4 select legs of the full run: add --full")
+    if args.dump_outputs and args.only not in (None, "place"):
+        ap.error("--dump-outputs writes the placement pass's results: not with --only "
+                 + args.only)
+    return args
+
+
+def dump_outputs(path, last, limit_bytes=64 << 20):
+    """--dump-outputs: the arrays the last timed placement pass returned to its
+    caller -- node.npy (placements, -1 unschedulable) and score.npy (integer
+    scores) --, as float64 (exact for both).  Above `limit_bytes` in all, the
+    same seeded sample of pods from every array.  Returns what was written."""
+    os.makedirs(path, exist_ok=True)
+    n = len(next(iter(last.values())))
+    keep = limit_bytes // (8 * len(last))
+    idx = None
+    if n > keep:
+        idx = np.sort(np.random.default_rng(SEED).choice(n, keep, replace=False))
+    for name, a in last.items():
+        a = np.asarray(a).reshape(-1)
+        np.save(os.path.join(path, name + ".npy"),
+                (a if idx is None else a[idx]).astype(np.float64))
+    return {"dir": os.path.abspath(path), "arrays": sorted(last), "dtype": "float64",
+            "pods": n if idx is None else keep,
+            "sample": None if idx is None else f"{keep} of {n} pods, seeded"}
 
 
 def _cgroup_cpus():
@@ -156,9 +198,10 @@ def pmc_traffic(args, profile=0):
     prof = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
     if not os.path.exists(prof):
         return {}, "rocprofv3 not found"
-    child = [sys.executable, os.path.abspath(__file__), "--only", "pmc", "--steps", "1",
-             "--warmup", "0", "--no-pmc", "--nodes", str(args.nodes), "--pods", str(args.pods),
-             "--dtype", args.dtype, "--peers", str(args.peers), "--synth-profile", str(profile)]
+    child = [sys.executable, os.path.abspath(__file__), "--full", "--only", "pmc",
+             "--steps", "1", "--warmup", "0", "--no-pmc", "--nodes", str(args.nodes),
+             "--pods", str(args.pods), "--dtype", args.dtype, "--peers", str(args.peers),
+             "--synth-profile", str(profile)]
     if profile != args.synth_profile:  # (a config line's inputs: the score leg only)
         child.append("--no-reference-mode")
     out = {}
@@ -374,8 +417,9 @@ def time_steps(d, fn, steps, warmup):
 
 
 def bench_place(args, d, eng):
-    """Returns (elapsed, per-stage times, placements, the engine to use from
-    here on, how the node shards exchange their lists)."""
+    """Returns (elapsed, per-stage times, placements, the last timed step's
+    results when --dump-outputs asks for them, the engine to use from here on,
+    how the node shards exchange their lists)."""
     N, P = args.nodes, args.pods
     if args.rehearse_world > 1:
         assert d.world == 1, "--rehearse-world runs on one GPU"
@@ -444,14 +488,17 @@ def bench_place(args, d, eng):
     elapsed = time_steps(d, step, args.steps, 0)
     eng.set_option("STAGE_TIMINGS", 1)
     per = {k: v / args.steps for k, v in acc.items()}
-    for k in keys:
-        acc[k] = 0.0
-    n_stage = 3
-    for _ in range(n_stage):
-        step()
-    per.update({k: acc[k] / n_stage for k in ("cost_ms", "fit_ms", "merge_ms", "commit_ms",
-                                                "total_ms")})
-    return elapsed, per, state["node"], eng, exchange
+    # the last timed step's results, before any later step reuses the arrays
+    last = {"node": outs[0].copy(), "score": outs[2].copy()} if args.dump_outputs else None
+    if args.full:
+        for k in keys:
+            acc[k] = 0.0
+        n_stage = 3
+        for _ in range(n_stage):
+            step()
+        per.update({k: acc[k] / n_stage for k in ("cost_ms", "fit_ms", "merge_ms", "commit_ms",
+                                                    "total_ms")})
+    return elapsed, per, state["node"], last, eng, exchange
 
 
 def bench_place_host(args, d, eng):
@@ -461,18 +508,19 @@ def bench_place_host(args, d, eng):
     from kubernetesnetawarescheduler_amd import sharded
     P = args.pods
     ag = host_all_gather(d)
-    state = {"node": None, "rounds": 0}
+    state = {"node": None, "score": None, "rounds": 0}
 
     def step():
         eng.reset_capacity()
-        node, _, rounds = sharded.place_dist_shard(eng, P, ag)
-        state["node"], state["rounds"] = node, rounds
+        node, score, rounds = sharded.place_dist_shard(eng, P, ag)
+        state["node"], state["score"], state["rounds"] = node, score, rounds
 
     elapsed = time_steps(d, step, args.steps, args.warmup)
     per = {"cost_ms": 0.0, "fit_ms": 0.0, "merge_ms": 0.0, "commit_ms": 0.0, "total_ms": 0.0,
            "rescore_rounds": float(state["rounds"]),
            "unschedulable": float((state["node"] < 0).sum())}
-    return elapsed, per, state["node"]
+    last = {"node": state["node"], "score": state["score"]} if args.dump_outputs else None
+    return elapsed, per, state["node"], last
 
 
 def bench_cost_kernel(args, d, eng):
@@ -1188,8 +1236,9 @@ def main():
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))
     result_out = _claim_stdout()
+    full = args.full
     traffic, traffic_why = {}, "not collected (--no-pmc or a multi-GPU run)"
-    if (not args.no_pmc and args.only is None and args.gpus == 1
+    if (args.full and not args.no_pmc and args.only is None and args.gpus == 1
             and int(os.environ.get("WORLD_SIZE", "1")) == 1):
         traffic, traffic_why = pmc_traffic(args)  # before this process initialises the GPU
         if not args.no_configs and args.dtype == "i8" and args.synth_profile == 0:
@@ -1222,21 +1271,24 @@ def main():
                             "its node columns scored, the other ranks' lists stood in for by "
                             "shifted copies; NOT a multi-GPU measurement, placements not checked")
     if args.only not in ("vote", "score", "pmc"):
-        elapsed, per, gpu_nodes, eng, exchange = bench_place(args, d, eng)
+        elapsed, per, gpu_nodes, last, eng, exchange = bench_place(args, d, eng)
         if exchange:
             out["config"]["exchange"] = exchange
         out["value"] = P * N / (elapsed / args.steps)
         out["ms_per_step"] = elapsed * 1e3 / args.steps
         out["placements_per_s"] = P / (elapsed / args.steps)
-        out["stages_ms"] = {k: per[k] for k in ("fit_ms", "cost_ms", "merge_ms", "commit_ms",
-                                                "total_ms")}
-        out["stages_note"] = ("device-side sums per step (3 extra steps with stage timings on; "
-                              "the timed steps record only synchronising events); scoring runs "
-                              "in chunks on two streams with merge + commit pipelined on a "
-                              "third, so stages overlap")
+        if full:
+            out["stages_ms"] = {k: per[k] for k in ("fit_ms", "cost_ms", "merge_ms", "commit_ms",
+                                                    "total_ms")}
+            out["stages_note"] = ("device-side sums per step (3 extra steps with stage timings "
+                                  "on; the timed steps record only synchronising events); "
+                                  "scoring runs in chunks on two streams with merge + commit "
+                                  "pipelined on a third, so stages overlap")
         out["rescore_rounds"] = per["rescore_rounds"]
         out["unschedulable"] = per["unschedulable"]
-    if args.only not in ("vote",):
+        if last is not None and d.rank == 0:
+            out["outputs"] = dump_outputs(args.dump_outputs, last)
+    if full and args.only not in ("vote",):
         if gpu_nodes is None:
             eng.synth_cluster(SEED, N, P, args.dtype, peers=args.peers, profile=args.synth_profile)
         cost_ms, samples = bench_cost_kernel(args, d, eng)
@@ -1264,12 +1316,12 @@ def main():
                                    "it with the rocprofv3 kernel trace of the same command"}
         if d.gpu and d.world == 1 and args.only is None:
             out["roofline"]["vendor_gemm"] = vendor_gemm_reference(args, d)
-    if args.only not in ("vote",) and d.gpu:
+    if full and args.only not in ("vote",) and d.gpu:
         fr = bench_fit_kernel(args, d, eng)
         fr["traffic"] = traffic.get("k_fit", {}).get("bytes")
         fr["traffic_unit"] = "B/launch"
         out["fit_roofline"] = fr
-    if not args.no_reference_mode and args.only in (None, "vote", "pmc"):
+    if full and not args.no_reference_mode and args.only in (None, "vote", "pmc"):
         elapsed, vote_ms, S, ref = bench_vote(args, d, eng)
         pods_total = S if args.vote_node_shard else S * d.world
         nloc = (d.rank + 1) * N // d.world - d.rank * N // d.world if args.vote_node_shard else N
@@ -1290,14 +1342,15 @@ def main():
         if (d.rank == 0 and d.world == 1 and not args.no_cpu_baseline and not args.vote_node_shard
                 and args.only != "pmc"):
             out["reference_mode"]["cpu_baseline"] = cpu_baseline_vote(args, eng, ref)
-    if d.rank == 0 and d.world == 1 and not args.no_cpu_baseline and gpu_nodes is not None:
+    if (full and d.rank == 0 and d.world == 1 and not args.no_cpu_baseline
+            and gpu_nodes is not None):
         # the vote path freed nothing; re-synthesise the cluster inputs (same seed)
         eng.synth_cluster(SEED, N, P, args.dtype, peers=args.peers, profile=args.synth_profile)
         out["cpu_baseline"] = cpu_baseline_place(args, eng, gpu_nodes)
     eng.close()
-    if d.world == 1 and not args.no_configs and args.only is None:
+    if full and d.world == 1 and not args.no_configs and args.only is None:
         out["configs"] = run_configs(args, d)
-    if d.rank == 0 and d.world == 1 and args.only is None and not args.no_configs:
+    if full and d.rank == 0 and d.world == 1 and args.only is None and not args.no_configs:
         out["host"] = bench_host(args)
     if args.c4 and "C4" not in out.get("configs", {}):
         from kubernetesnetawarescheduler_amd import Engine

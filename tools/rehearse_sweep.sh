@@ -5,7 +5,7 @@
 set -uo pipefail
 OUT=$(realpath -m "$1"); ROOT=$GRAFT_REPO_ROOT
 mkdir -p "$OUT"
-B="--only place --no-cpu-baseline --no-pmc --no-configs --no-reference-mode"
+B="--full --only place --no-cpu-baseline --no-pmc --no-configs --no-reference-mode"
 ( cd /tmp && export TMPDIR=/tmp && timeout -k 10 200 rocprofv3 --kernel-trace --output-format csv -d "$OUT/tr8" -o t \
     -- python3 "$ROOT/bench.py" $B --rehearse-world 8 --steps 5 --warmup 2 > "$OUT/g8.json" 2>&1 ) || { echo "trace failed"; exit 1; }
 python3 tools/pass_timeline.py "$OUT/tr8" > "$OUT/g8_timeline.txt"
