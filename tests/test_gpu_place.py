@@ -324,7 +324,7 @@ def test_rescore_slots_across_chunks(engine):
 
 @pytest.mark.parametrize("P", [20000, 6000])
 def test_l2_commit_published_capacity(engine, P):
-    """More nodes than the LDS commit holds (N > 13,610): the commit works on
+    """More nodes than the LDS commit holds (N > 11,541): the commit works on
     the capacity in L2 with speculative reservations, and the pipelined
     scoring chunks read the published capacity it maintains (start minus
     committed pods).  Crowded preferences and 2 pod slots per node make many

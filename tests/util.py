@@ -117,3 +117,68 @@ def usable(keys, bound):
     ok = (keys != KEY_INVALID) & (keys <= bound[:, None])
     nodes = np.where(ok, (keys & np.uint64(0xFFFFFFFF)).astype(np.int64), -1).astype(np.int32)
     return nodes, ok.sum(axis=1).astype(np.int32)
+
+
+ZERO_COST_HI = 0x80000000  # high word of every key of a zero-traffic pod (cost 0)
+
+
+def commit_ref(keys, bounds, req, free, zero, p_begin, want_dist=False):
+    """The commit contract (k_commit.hip's header, include/nas.h nas_commit) in
+    plain Python: pods in order from p_begin; a pod's usable candidates are its
+    keys != KEY_INVALID and <= its bound; it takes the first usable candidate
+    whose node fits all three resources NOW (int64 capacity, decremented), with
+    the key's decoded high word as score.  When none fits: a complete list
+    (bound == KEY_INVALID) gives node -1, score 0; a zero-traffic pod whose
+    bound's high word is the cost-0 word takes the first node above the
+    bound's node that fits now (score 0), or -1 when none fits up to N - 1;
+    any other pod stops the walk.
+
+    keys (P, 8) / bounds (P,) uint64, req (P, 3), free (N, 3), zero (P,) bool.
+    Returns (node, score, free_after, stop); entries outside [p_begin, stop)
+    are -3 / 0.  want_dist adds dist (P,): -1 for a pod that was not scanned,
+    else the nodes its scan walked past the bound's node -- the distance to
+    the node it took, or N - 1 - (bound's node) when nothing fitted."""
+    K = np.asarray(keys, np.uint64).tolist()
+    B = np.asarray(bounds, np.uint64).tolist()
+    R = np.asarray(req, np.int64).tolist()
+    Z = np.asarray(zero, bool).tolist()
+    cap = np.asarray(free, np.int64).tolist()
+    P, N = len(B), len(cap)
+    node = np.full(P, -3, np.int32)
+    score = np.zeros(P, np.int64)
+    dist = np.full(P, -1, np.int64)
+    stop = commit_walk(K, B, R, Z, cap, p_begin, node, score, dist)
+    out = (node, score, np.array(cap, np.int64).reshape(N, 3), stop)
+    return out + (dist,) if want_dist else out
+
+
+def commit_walk(K, B, R, Z, cap, p_begin, node, score, dist):
+    """commit_ref's walk on Python lists (cap is updated in place; node, score
+    and dist are arrays to fill); returns the stop pod."""
+    inv = int(KEY_INVALID)
+    P, N = len(B), len(cap)
+
+    def fits(r, c):
+        return r[0] <= c[0] and r[1] <= c[1] and r[2] <= c[2]
+
+    for p in range(p_begin, P):
+        b, r = B[p], R[p]
+        n, s = -1, 0
+        for k in K[p]:
+            if k == inv or k > b:
+                continue
+            if fits(r, cap[k & 0xFFFFFFFF]):
+                n = k & 0xFFFFFFFF
+                s = (k >> 32) ^ 0x80000000
+                s -= (s >> 31) << 32  # as int32
+                break
+        if n < 0 and b != inv:
+            if not (Z[p] and (b >> 32) == ZERO_COST_HI):
+                return p
+            bn = b & 0xFFFFFFFF
+            n = next((m for m in range(bn + 1, N) if fits(r, cap[m])), -1)
+            dist[p] = (n if n >= 0 else N - 1) - bn
+        node[p], score[p] = n, s
+        if n >= 0:
+            cap[n] = [c - x for c, x in zip(cap[n], r)]
+    return P
