@@ -302,6 +302,34 @@ int nas_get_capacity(nas_ctx *ctx, int32_t *cpu_milli, int32_t *mem_kib, int32_t
 int nas_upload_pods(nas_ctx *ctx, const int32_t *req_cpu_milli, const int32_t *req_mem_kib,
                     const int32_t *req_pods, int32_t P);
 
+/* ---- node selectors and taints: per-pod node eligibility -------------------
+ * Two 64-bit words per node (labels, taints) and two per pod (require,
+ * tolerate):
+ *   eligible(p, n) <=> (labels[n] & require[p]) == require[p]
+ *                  and (taints[n] & ~tolerate[p]) == 0
+ * While constraints are uploaded, "fits" everywhere in this interface means
+ * eligible AND the three resources fit: nas_filter's bits, the candidate lists
+ * with their count / complete guarantees, nas_place, the host-driven
+ * nas_score_range / nas_commit steps and timings.unschedulable.  Eligibility
+ * is static during a pass; the placement is still the sequential greedy one.
+ * A side never uploaded counts as all zero (pod words alone: every non-zero
+ * require is unsatisfiable; node words alone: a tainted node is closed to all
+ * pods).  A NULL array is all zero.  The words persist across later uploads
+ * of the same shape until re-uploaded or cleared; a placement call with n !=
+ * the cluster's nodes or P != the uploaded pods fails with NAS_ERR_ARG.
+ * Node shards: every rank uploads the same full-length arrays.  Not with a
+ * cluster batch (NAS_ERR_UNSUPPORTED).  A constrained pass runs k_fit and the
+ * 256 x 256 cost tile instead of the fused fit / wide tile, without the
+ * cost-row cache and the commit's zero-traffic scan (README, options). */
+/* labels / taints: [n] each, NULL = all zero */
+int nas_upload_node_constraints(nas_ctx *ctx, const uint64_t *labels, const uint64_t *taints,
+                                int32_t n);
+/* require / tolerate: [P] each, NULL = all zero */
+int nas_upload_pod_constraints(nas_ctx *ctx, const uint64_t *require, const uint64_t *tolerate,
+                               int32_t P);
+/* back to resource fit only */
+int nas_clear_constraints(nas_ctx *ctx);
+
 /* Traffic of each pending pod to each node, WA[p * n + m] = sum of
  * W[p,q] over already-bound peers q with node(q) == m (dense).  dtype: the
  * latency's (NAS_DT_I8 / NAS_DT_BF16), or NAS_DT_I32 with NAS_DT_I8 latency --

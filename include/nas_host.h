@@ -172,6 +172,34 @@ int nas_host_schedule_batch(nas_host_sched *s, int32_t max_pods, nas_host_outcom
  * nas_host_queued() entries. */
 int nas_host_place_pending(nas_host_sched *s, nas_host_outcome *out, int32_t *n_out);
 
+/* ---- node selectors and taints (nas.h: nas_upload_*_constraints) -----------
+ * Strings match exactly: labels and selectors look like "key=value", taints
+ * and tolerations like "key=value:NoSchedule" (no Exists operator, no
+ * PreferNoSchedule).  A pod may be placed on a node only if the node carries
+ * every label of the pod's node selector and the pod tolerates every taint of
+ * the node.  Each call replaces what was set for that node / pod (0 strings:
+ * none); the pod's entry is keyed by "namespace/name" and stays until reset.
+ * nas_host_place_pending interns the strings to bits per call: a label gets a
+ * bit only if some pending pod selects it (a selected label no listed node
+ * carries still gets one, so that pod is ineligible everywhere), a taint only
+ * if some listed node carries it; more than 64 of either fails the call with
+ * a message naming the count.  It uploads the four word arrays, or clears
+ * the engine's constraints when none are set.  A pod with no eligible node at
+ * all is NAS_HOST_UNSCHEDULABLE with the message "no node matches the pod's
+ * node selector and tolerations"; every other unschedulable pod keeps "no
+ * node fits the pod's requests".  nas_host_schedule_one / _batch (the
+ * reference's vote) ignore constraints. */
+int nas_host_set_node_constraints(nas_host_sched *s, const char *node, const char *const *labels,
+                                  int32_t n_labels, const char *const *taints, int32_t n_taints);
+int nas_host_set_pod_constraints(nas_host_sched *s, const char *ns_name,
+                                 const char *const *node_selector, int32_t n_sel,
+                                 const char *const *tolerations, int32_t n_tol);
+/* pure, no scheduler: bit i of *bits_out is set iff universe[i] is among
+ * have[0 .. n_have); a `have` string outside the universe is ignored.
+ * NAS_ERR_ARG for a universe of more than 64 strings. */
+int nas_host_intern_bits(const char *const *universe, int32_t n_universe, const char *const *have,
+                         int32_t n_have, uint64_t *bits_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -100,6 +100,9 @@ SIGNATURES = {
     "nas_reset_capacity": (_I, [_CTX]),
     "nas_get_capacity": (_I, [_CTX, _V, _V, _V, _I]),
     "nas_upload_pods": (_I, [_CTX, _V, _V, _V, _I]),
+    "nas_upload_node_constraints": (_I, [_CTX, _V, _V, _I]),
+    "nas_upload_pod_constraints": (_I, [_CTX, _V, _V, _I]),
+    "nas_clear_constraints": (_I, [_CTX]),
     "nas_upload_traffic_dense": (_I, [_CTX, _V, _I, _I, _I]),
     "nas_upload_traffic_csr": (_I, [_CTX, _V, _V, _V, _I, _I, _I, _c.c_int64]),
     "nas_filter": (_I, [_CTX, _V]),

@@ -20,6 +20,19 @@
 // Requests are small against node capacity until nodes fill up, so most
 // (pod, chunk) pairs cost 1/64 of a compare; the kernel runs near the rate of
 // its mask write (P*N/8 bytes, HBM) -- see DESIGN.md.
+//
+// Constrained form (C = true, nas::Elig: node selectors and taints): the lane
+// also keeps its node's label and taint words in VGPRs, the wave the chunk's
+// AND / OR of each (wave-uniform, padding lanes excluded), and a pod's
+// require / tolerate words travel with its requests.  eligible(p, n) <=>
+// (labels[n] & require[p]) == require[p] and (taints[n] & ~tolerate[p]) == 0:
+//   * "fits every valid node" also needs require & ~AND(labels) == 0 and
+//     OR(taints) & ~tolerate == 0;
+//   * "fits none" also holds when require & ~OR(labels) != 0 or
+//     AND(taints) & ~tolerate != 0;
+//   * the remaining pods take two more ballots each.
+// The unconstrained kernels are the C = false instantiations of the same
+// bodies (every constrained statement sits under `if constexpr (C)`).
 #include "nas_internal.h"
 
 namespace nas {
@@ -29,18 +42,38 @@ constexpr int FIT_THREADS = 256;  // 4 waves = 4 node chunks per block
 constexpr int FIT_WAVES = FIT_THREADS / 64;
 constexpr int FIT_GROUPS_MAX = 8;  // 64-pod groups per block (at most 512 pods)
 constexpr int FIT_PF = 2;          // groups of requests in flight ahead of the one decided
+typedef unsigned long long u64;
+
+// the chunk's AND / OR of a per-node word over its valid lanes, wave-uniform
+__device__ __forceinline__ u64 wave_and(u64 v) {
+#pragma unroll
+    for (int o = 32; o; o >>= 1) v &= __shfl_xor(v, o);
+    return ((u64)(unsigned)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) |
+           (unsigned)__builtin_amdgcn_readfirstlane((int)v);
+}
+__device__ __forceinline__ u64 wave_or(u64 v) {
+#pragma unroll
+    for (int o = 32; o; o >>= 1) v |= __shfl_xor(v, o);
+    return ((u64)(unsigned)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) |
+           (unsigned)__builtin_amdgcn_readfirstlane((int)v);
+}
+// lane i's 64-bit word, wave-uniform
+__device__ __forceinline__ u64 readlane64(u64 v, int i) {
+    return ((u64)(unsigned)__builtin_amdgcn_readlane((int)(v >> 32), i) << 32) |
+           (unsigned)__builtin_amdgcn_readlane((int)v, i);
+}
 
 // G = 64-pod groups per wave (compile time: the group loop is unrolled and the
 // request ring stays in registers).  Measured at the C3 shape (10k nodes x 100k
 // pods, tools/mb_fit.hip): 29.0 us for the round-2 kernel (runtime group loop,
 // one group prefetched), 25.5 us unrolled with the uniform bounds in SGPRs,
 // 24.5 us with non-temporal mask stores (the mask is written once).
-template <int G>
-__global__ void __launch_bounds__(FIT_THREADS)
-k_fit(const int *cap, int N, int n0, int nloc, int n_chunks,
-      const int *__restrict__ req, int Pp, int p0, int p_end, unsigned long long *__restrict__ mask,
-      const int *__restrict__ dyn_start, int dyn_win, const int *__restrict__ dyn_hi_ptr,
-      const int *__restrict__ rowmap, int rs) {
+template <int G, bool C>
+__device__ __forceinline__ void
+fit_body(const int *cap, int N, int n0, int nloc, int n_chunks,
+         const int *__restrict__ req, int Pp, int p0, int p_end, unsigned long long *__restrict__ mask,
+         const int *__restrict__ dyn_start, int dyn_win, const int *__restrict__ dyn_hi_ptr,
+         const int *__restrict__ rowmap, int rs, const Elig &el) {
     // rowmap (gathered rescore view): row q's requests are pod rowmap[q]'s,
     // in the main request array (row stride rs); the mask keeps view rows
     if (dyn_start) {  // window [*dyn_start, +dyn_win) read from device memory (rescore slots)
@@ -67,12 +100,17 @@ k_fit(const int *cap, int N, int n0, int nloc, int n_chunks,
     auto row = [&](int r) { const int q = min(r, p_end - 1); return rowmap ? rowmap[q] : q; };
     constexpr int RING = FIT_PF + 1 < G ? FIT_PF + 1 : G;
     int ra[RING], rb[RING], rd[RING];
+    u64 rq[C ? RING : 1], rt[C ? RING : 1];  // (constrained) the pod's require / tolerate words
 #pragma unroll
     for (int g = 0; g < RING; ++g) {
         const int q = row(pb0 + 64 * g + lane);
         ra[g] = req[q];
         rb[g] = req[rs + q];
         rd[g] = req[2 * (size_t)rs + q];
+        if constexpr (C) {
+            rq[g] = el.require[q];
+            rt[g] = el.tolerate[q];
+        }
     }
     // relaxed atomic loads: nas_place filters against the working capacity
     // while the commit stream publishes into it; padding nodes never fit
@@ -105,6 +143,19 @@ k_fit(const int *cap, int N, int n0, int nloc, int n_chunks,
     xc = __builtin_amdgcn_readfirstlane(xc);
     xm = __builtin_amdgcn_readfirstlane(xm);
     xp = __builtin_amdgcn_readfirstlane(xp);
+    // (constrained) the node's label / taint words and the chunk's AND / OR of
+    // each over its valid nodes
+    u64 lb = 0, tn = 0, l_and = 0, l_or = 0, t_and = 0, t_or = 0;
+    if constexpr (C) {
+        if (real) {
+            lb = el.labels[n0 + nl];
+            tn = el.taints[n0 + nl];
+        }
+        l_and = wave_and(real ? lb : ~0ull);
+        l_or = wave_or(lb);
+        t_and = wave_and(real ? tn : ~0ull);
+        t_or = wave_or(tn);
+    }
     const unsigned vlo = (unsigned)valid, vhi = (unsigned)(valid >> 32);
 #pragma unroll
     for (int g = 0; g < G; ++g) {
@@ -112,17 +163,30 @@ k_fit(const int *cap, int N, int n0, int nloc, int n_chunks,
         if (pb >= pend) break;
         const int sl = g % RING;
         const int a0 = ra[sl], b0 = rb[sl], d0 = rd[sl];
+        const u64 q0 = C ? rq[C ? sl : 0] : 0, t0 = C ? rt[C ? sl : 0] : 0;
         if (g + RING < G) {  // refill the slot just consumed
             const int q = row(pb + 64 * RING + lane);
             ra[sl] = req[q];
             rb[sl] = req[rs + q];
             rd[sl] = req[2 * (size_t)rs + q];
+            if constexpr (C) {
+                rq[sl] = el.require[q];
+                rt[sl] = el.tolerate[q];
+            }
         }
         const bool in = pb + lane < pend;
         // 64 pods at once against the chunk's extremes: fits every valid node
         // (requests <= the minima) or none (some request > its maximum)
-        const unsigned long long all = __builtin_amdgcn_ballot_w64(in && a0 <= mc && b0 <= mm && d0 <= mp);
-        const unsigned long long none = __builtin_amdgcn_ballot_w64(in && (a0 > xc || b0 > xm || d0 > xp));
+        unsigned long long all, none;
+        if constexpr (C) {
+            all = __builtin_amdgcn_ballot_w64(in && a0 <= mc && b0 <= mm && d0 <= mp &&
+                                              (q0 & ~l_and) == 0 && (t_or & ~t0) == 0);
+            none = __builtin_amdgcn_ballot_w64(in && (a0 > xc || b0 > xm || d0 > xp ||
+                                                      (q0 & ~l_or) != 0 || (t_and & ~t0) != 0));
+        } else {
+            all = __builtin_amdgcn_ballot_w64(in && a0 <= mc && b0 <= mm && d0 <= mp);
+            none = __builtin_amdgcn_ballot_w64(in && (a0 > xc || b0 > xm || d0 > xp));
+        }
         unsigned long long rest = __builtin_amdgcn_ballot_w64(in) & ~all & ~none;
         unsigned lo = ((all >> lane) & 1) ? vlo : 0u, hi = ((all >> lane) & 1) ? vhi : 0u;
         // the others one by one: the pod's (broadcast) requests against the
@@ -132,9 +196,14 @@ k_fit(const int *cap, int N, int n0, int nloc, int n_chunks,
             rest &= rest - 1;
             const int a = __builtin_amdgcn_readlane(a0, i), b = __builtin_amdgcn_readlane(b0, i);
             const int d = __builtin_amdgcn_readlane(d0, i);
-            const unsigned long long m = __builtin_amdgcn_ballot_w64(a <= fc) &
-                                         __builtin_amdgcn_ballot_w64(b <= fm) &
-                                         __builtin_amdgcn_ballot_w64(d <= fp);
+            unsigned long long m = __builtin_amdgcn_ballot_w64(a <= fc) &
+                                   __builtin_amdgcn_ballot_w64(b <= fm) &
+                                   __builtin_amdgcn_ballot_w64(d <= fp);
+            if constexpr (C) {
+                const u64 qi = readlane64(q0, i), ti = readlane64(t0, i);
+                m &= __builtin_amdgcn_ballot_w64((lb & qi) == qi) &
+                     __builtin_amdgcn_ballot_w64((tn & ~ti) == 0);
+            }
             if (lane == i) {
                 lo = (unsigned)m;
                 hi = (unsigned)(m >> 32);
@@ -146,17 +215,39 @@ k_fit(const int *cap, int N, int n0, int nloc, int n_chunks,
     }
 }
 
+template <int G>
+__global__ void __launch_bounds__(FIT_THREADS)
+k_fit(const int *cap, int N, int n0, int nloc, int n_chunks,
+      const int *__restrict__ req, int Pp, int p0, int p_end, unsigned long long *__restrict__ mask,
+      const int *__restrict__ dyn_start, int dyn_win, const int *__restrict__ dyn_hi_ptr,
+      const int *__restrict__ rowmap, int rs) {
+    fit_body<G, false>(cap, N, n0, nloc, n_chunks, req, Pp, p0, p_end, mask, dyn_start, dyn_win,
+                       dyn_hi_ptr, rowmap, rs, Elig{});
+}
+
+// the constrained form: fits <=> eligible and the three resources fit
+template <int G>
+__global__ void __launch_bounds__(FIT_THREADS)
+k_fit_c(const int *cap, int N, int n0, int nloc, int n_chunks,
+        const int *__restrict__ req, int Pp, int p0, int p_end, unsigned long long *__restrict__ mask,
+        const int *__restrict__ dyn_start, int dyn_win, const int *__restrict__ dyn_hi_ptr,
+        const int *__restrict__ rowmap, int rs, const Elig el) {
+    fit_body<G, true>(cap, N, n0, nloc, n_chunks, req, Pp, p0, p_end, mask, dyn_start, dyn_win,
+                      dyn_hi_ptr, rowmap, rs, el);
+}
+
 // Two pods per lane (pods pb + 2i and pb + 2i + 1 of a 128-pod group): the
 // requests arrive as one 8-byte load per resource and the two fit words leave
 // as ONE 16-byte store per lane -- half the memory instructions of k_fit per
 // pod for the same bytes.  Same decisions as k_fit (the chunk's extremes
 // first, then the remaining pods one by one); main pod ranges only (no row
 // map: a gathered view's rows are not adjacent).
-template <int G>
-__global__ void __launch_bounds__(FIT_THREADS)
-k_fit2(const int *cap, int N, int n0, int nloc, int n_chunks,
-       const int *__restrict__ req, int Pp, int p0, int p_end, unsigned long long *__restrict__ mask,
-       const int *__restrict__ dyn_start, int dyn_win, const int *__restrict__ dyn_hi_ptr) {
+template <int G, bool C>
+__device__ __forceinline__ void
+fit2_body(const int *cap, int N, int n0, int nloc, int n_chunks,
+          const int *__restrict__ req, int Pp, int p0, int p_end, unsigned long long *__restrict__ mask,
+          const int *__restrict__ dyn_start, int dyn_win, const int *__restrict__ dyn_hi_ptr,
+          const Elig &el) {
     if (dyn_start) {
         const int s = dyn_start[blockIdx.z * STATUS_INTS];
         if (s < 0) return;
@@ -202,13 +293,31 @@ k_fit2(const int *cap, int N, int n0, int nloc, int n_chunks,
     xc = __builtin_amdgcn_readfirstlane(xc);
     xm = __builtin_amdgcn_readfirstlane(xm);
     xp = __builtin_amdgcn_readfirstlane(xp);
+    u64 lb = 0, tn = 0, l_and = 0, l_or = 0, t_and = 0, t_or = 0;  // (constrained, as in fit_body)
+    if constexpr (C) {
+        if (real) {
+            lb = el.labels[n0 + nl];
+            tn = el.taints[n0 + nl];
+        }
+        l_and = wave_and(real ? lb : ~0ull);
+        l_or = wave_or(lb);
+        t_and = wave_and(real ? tn : ~0ull);
+        t_or = wave_or(tn);
+    }
+    typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
     // requests of the lane's two pods (8-byte loads; rows past the range read
-    // the last even pair, loaded, never stored)
+    // the last even pair, loaded, never stored); constrained: their require /
+    // tolerate words too (16-byte loads)
+    u64x2 rq = {0, 0}, rt = {0, 0};
     auto load2 = [&](int pb, int2 &a, int2 &b, int2 &d) {
         const int q = min(pb + 2 * lane, (p_end - 1) & ~1);
         a = *reinterpret_cast<const int2 *>(req + q);
         b = *reinterpret_cast<const int2 *>(req + Pp + q);
         d = *reinterpret_cast<const int2 *>(req + 2 * (size_t)Pp + q);
+        if constexpr (C) {
+            rq = *reinterpret_cast<const u64x2 *>(el.require + q);
+            rt = *reinterpret_cast<const u64x2 *>(el.tolerate + q);
+        }
     };
     int2 ra, rb, rd;
     load2(pb0, ra, rb, rd);
@@ -217,6 +326,7 @@ k_fit2(const int *cap, int N, int n0, int nloc, int n_chunks,
         const int pb = pb0 + 128 * g;
         if (pb >= pend) break;
         const int2 a0 = ra, b0 = rb, d0 = rd;
+        const u64x2 q0 = rq, t0 = rt;
         if (g + 1 < G) load2(pb + 128, ra, rb, rd);  // next group in flight
         const bool in0 = pb + 2 * lane < pend, in1 = pb + 2 * lane + 1 < pend;
         unsigned long long w0 = 0, w1 = 0;
@@ -225,9 +335,17 @@ k_fit2(const int *cap, int N, int n0, int nloc, int n_chunks,
         for (int h = 0; h < 2; ++h) {
             const int a = h ? a0.y : a0.x, b = h ? b0.y : b0.x, d = h ? d0.y : d0.x;
             const bool in = h ? in1 : in0;
-            const unsigned long long all = __builtin_amdgcn_ballot_w64(in && a <= mc && b <= mm && d <= mp);
-            const unsigned long long none =
-                __builtin_amdgcn_ballot_w64(in && (a > xc || b > xm || d > xp));
+            const u64 pq = h ? q0.y : q0.x, pt = h ? t0.y : t0.x;
+            unsigned long long all, none;
+            if constexpr (C) {
+                all = __builtin_amdgcn_ballot_w64(in && a <= mc && b <= mm && d <= mp &&
+                                                  (pq & ~l_and) == 0 && (t_or & ~pt) == 0);
+                none = __builtin_amdgcn_ballot_w64(in && (a > xc || b > xm || d > xp ||
+                                                          (pq & ~l_or) != 0 || (t_and & ~pt) != 0));
+            } else {
+                all = __builtin_amdgcn_ballot_w64(in && a <= mc && b <= mm && d <= mp);
+                none = __builtin_amdgcn_ballot_w64(in && (a > xc || b > xm || d > xp));
+            }
             unsigned long long rest = __builtin_amdgcn_ballot_w64(in) & ~all & ~none;
             unsigned long long word = ((all >> lane) & 1) ? valid : 0ull;
             while (rest) {
@@ -235,9 +353,14 @@ k_fit2(const int *cap, int N, int n0, int nloc, int n_chunks,
                 rest &= rest - 1;
                 const int ba = __builtin_amdgcn_readlane(a, i), bb = __builtin_amdgcn_readlane(b, i);
                 const int bd = __builtin_amdgcn_readlane(d, i);
-                const unsigned long long m = __builtin_amdgcn_ballot_w64(ba <= fc) &
-                                             __builtin_amdgcn_ballot_w64(bb <= fm) &
-                                             __builtin_amdgcn_ballot_w64(bd <= fp);
+                unsigned long long m = __builtin_amdgcn_ballot_w64(ba <= fc) &
+                                       __builtin_amdgcn_ballot_w64(bb <= fm) &
+                                       __builtin_amdgcn_ballot_w64(bd <= fp);
+                if constexpr (C) {
+                    const u64 qi = readlane64(pq, i), ti = readlane64(pt, i);
+                    m &= __builtin_amdgcn_ballot_w64((lb & qi) == qi) &
+                         __builtin_amdgcn_ballot_w64((tn & ~ti) == 0);
+                }
                 if (lane == i) word = m;
             }
             if (h) w1 = word;
@@ -247,7 +370,6 @@ k_fit2(const int *cap, int N, int n0, int nloc, int n_chunks,
         // plain stores: 24.7-24.9 vs 25.1-25.8 us for non-temporal ones at the
         // C3 shape (profiles/r04_ab_fold.txt, fitpl)
         if (in1) {
-            typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
             *reinterpret_cast<u64x2 *>(dst) = u64x2{w0, w1};
         } else if (in0) {
             *dst = w0;
@@ -255,13 +377,37 @@ k_fit2(const int *cap, int N, int n0, int nloc, int n_chunks,
     }
 }
 
+template <int G>
+__global__ void __launch_bounds__(FIT_THREADS)
+k_fit2(const int *cap, int N, int n0, int nloc, int n_chunks,
+       const int *__restrict__ req, int Pp, int p0, int p_end, unsigned long long *__restrict__ mask,
+       const int *__restrict__ dyn_start, int dyn_win, const int *__restrict__ dyn_hi_ptr) {
+    fit2_body<G, false>(cap, N, n0, nloc, n_chunks, req, Pp, p0, p_end, mask, dyn_start, dyn_win,
+                        dyn_hi_ptr, Elig{});
+}
+
+template <int G>
+__global__ void __launch_bounds__(FIT_THREADS)
+k_fit2_c(const int *cap, int N, int n0, int nloc, int n_chunks,
+         const int *__restrict__ req, int Pp, int p0, int p_end, unsigned long long *__restrict__ mask,
+         const int *__restrict__ dyn_start, int dyn_win, const int *__restrict__ dyn_hi_ptr,
+         const Elig el) {
+    fit2_body<G, true>(cap, N, n0, nloc, n_chunks, req, Pp, p0, p_end, mask, dyn_start, dyn_win,
+                       dyn_hi_ptr, el);
+}
+
 }  // namespace
 
 hipError_t launch_fit(hipStream_t st, const int32_t *cap, int N, int n0, int nloc, int Mp,
                       const int32_t *req, int P, int Pp, int p0, int np, uint64_t *mask,
-                      const Dyn *dyn, int batch, const int32_t *rowmap, int req_stride) {
+                      const Dyn *dyn, int batch, const int32_t *rowmap, int req_stride,
+                      const Elig *el) {
     (void)P;
     if (rowmap && batch != 1) return hipErrorInvalidValue;
+    // the constraint words are one cluster's: [N] per node, [Pp] per pod of the
+    // main pod array (a row-mapped view reads them through its row map)
+    if (el && (batch != 1 || !el->labels || !el->taints || !el->require || !el->tolerate))
+        return hipErrorInvalidValue;
     if (np <= 0) return hipSuccess;
     const int n_chunks = Mp / 64;
     if (!rowmap && p0 % 2 == 0) {  // two pods per lane (k_fit2)
@@ -275,8 +421,12 @@ hipError_t launch_fit(hipStream_t st, const int32_t *cap, int N, int n0, int nlo
         const int pe2 = dyn ? dyn->hi : p0 + np;
         const int *ds2 = dyn ? dyn->start : nullptr, *dh2 = dyn ? dyn->hi_ptr : nullptr;
         const int dw2 = dyn ? dyn->win : 0;
-#define NAS_FIT2(GV) \
-    k_fit2<GV><<<grid2, FIT_THREADS, 0, st>>>(cap, N, n0, nloc, n_chunks, req, Pp, p0, pe2, m2, ds2, dw2, dh2)
+#define NAS_FIT2(GV)                                                                                 \
+    if (el)                                                                                          \
+        k_fit2_c<GV><<<grid2, FIT_THREADS, 0, st>>>(cap, N, n0, nloc, n_chunks, req, Pp, p0, pe2, m2, \
+                                                    ds2, dw2, dh2, *el);                             \
+    else                                                                                             \
+        k_fit2<GV><<<grid2, FIT_THREADS, 0, st>>>(cap, N, n0, nloc, n_chunks, req, Pp, p0, pe2, m2, ds2, dw2, dh2)
         switch (G2) {
         case 4: NAS_FIT2(4); break;
         case 2: NAS_FIT2(2); break;
@@ -297,8 +447,12 @@ hipError_t launch_fit(hipStream_t st, const int32_t *cap, int N, int n0, int nlo
     const int pe = dyn ? dyn->hi : p0 + np;
     const int *ds = dyn ? dyn->start : nullptr, *dh = dyn ? dyn->hi_ptr : nullptr;
     const int dw = dyn ? dyn->win : 0, rs = rowmap ? req_stride : Pp;
-#define NAS_FIT(GV) \
-    k_fit<GV><<<grid, FIT_THREADS, 0, st>>>(cap, N, n0, nloc, n_chunks, req, Pp, p0, pe, m, ds, dw, dh, rowmap, rs)
+#define NAS_FIT(GV)                                                                                  \
+    if (el)                                                                                          \
+        k_fit_c<GV><<<grid, FIT_THREADS, 0, st>>>(cap, N, n0, nloc, n_chunks, req, Pp, p0, pe, m, ds, \
+                                                  dw, dh, rowmap, rs, *el);                          \
+    else                                                                                             \
+        k_fit<GV><<<grid, FIT_THREADS, 0, st>>>(cap, N, n0, nloc, n_chunks, req, Pp, p0, pe, m, ds, dw, dh, rowmap, rs)
     switch (G) {
     case 8: NAS_FIT(8); break;
     case 4: NAS_FIT(4); break;

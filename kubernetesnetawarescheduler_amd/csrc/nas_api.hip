@@ -332,10 +332,58 @@ int prepare_zrow(nas_ctx *ctx) {
 
 // the commit's zero-traffic flags, or nullptr when 0 x L may not be 0
 // (a float latency matrix holding Inf / NaN)
+// (nor while node selectors / taints are uploaded: the commit's capacity
+// scan knows nothing of eligibility, so the walk halts there instead and a
+// rescore -- through the constrained k_fit -- refreshes the pod's list)
+bool constrained(const nas_ctx *ctx) { return ctx->have_node_con || ctx->have_pod_con; }
 const uint8_t *zrow_ptr(const nas_ctx *ctx) {
     if (!ctx->zrow_valid || (ctx->dtype != NAS_DT_I8 && !ctx->L_finite)) return nullptr;
+    if (constrained(ctx)) return nullptr;
     return ctx->zrow.as<uint8_t>();
 }
+
+// Node selectors and taints (nas::Elig).  check_constraints: the uploaded
+// words match the cluster (n nodes, P pods); prepare_constraints: the side
+// that was never uploaded as all-zero words of the current shape, and
+// ctx->elig pointing at the four arrays; elig(): what launch_fit gets
+// (nullptr = resource fit only, today's kernels).
+int check_constraints(nas_ctx *ctx, int n, int P) {
+    if (!constrained(ctx)) return NAS_OK;
+    if (ctx->B > 1)
+        return nas::fail(ctx, NAS_ERR_UNSUPPORTED,
+                         "node selectors / taints with a cluster batch (nas_clear_constraints first)");
+    if (ctx->have_node_con && ctx->con_n != n)
+        return nas::fail(ctx, NAS_ERR_ARG,
+                         "node constraints were uploaded for " + std::to_string(ctx->con_n) +
+                             " nodes, the cluster has " + std::to_string(n));
+    if (ctx->have_pod_con && ctx->con_P != P)
+        return nas::fail(ctx, NAS_ERR_ARG,
+                         "pod constraints were uploaded for " + std::to_string(ctx->con_P) +
+                             " pods, " + std::to_string(P) + " pods are uploaded");
+    return NAS_OK;
+}
+
+int prepare_constraints(nas_ctx *ctx) {
+    if (!constrained(ctx)) return NAS_OK;
+    if (!ctx->have_node_con && ctx->con_zero_n != ctx->N) {
+        OK(nas::ensure(ctx, ctx->node_con, (size_t)2 * ctx->N * 8));
+        HIPCK(hipMemsetAsync(ctx->node_con.p, 0, (size_t)2 * ctx->N * 8, ctx->stream));
+        ctx->con_zero_n = ctx->N;
+    }
+    if (!ctx->have_pod_con && ctx->con_zero_Pp != ctx->Pp) {
+        OK(nas::ensure(ctx, ctx->pod_con, (size_t)2 * ctx->Pp * 8));
+        HIPCK(hipMemsetAsync(ctx->pod_con.p, 0, (size_t)2 * ctx->Pp * 8, ctx->stream));
+        ctx->con_zero_Pp = ctx->Pp;
+    }
+    const int64_t pp = ctx->have_pod_con ? ctx->con_Pp : ctx->Pp;
+    ctx->elig.labels = ctx->node_con.as<uint64_t>();
+    ctx->elig.taints = ctx->node_con.as<uint64_t>() + ctx->N;
+    ctx->elig.require = ctx->pod_con.as<uint64_t>();
+    ctx->elig.tolerate = ctx->pod_con.as<uint64_t>() + pp;
+    return NAS_OK;
+}
+
+const nas::Elig *elig(const nas_ctx *ctx) { return constrained(ctx) ? &ctx->elig : nullptr; }
 
 // NAS_DT_F32 scores on the bf16 MFMA: both operands split into six K-segments
 // of bf16 planes (k_misc.hip k_split6), once per upload; every cost launch
@@ -435,7 +483,7 @@ int check_extended(nas_ctx *ctx) {
                          "int8 path: a pod's sum_m |WA[p,m]| * max|L| = " +
                              std::to_string(ctx->wa_abs_row_max) + " * " +
                              std::to_string(ctx->L_abs_max) + " exceeds int32");
-    return NAS_OK;
+    return check_constraints(ctx, ctx->N, ctx->P);
 }
 
 void abort_comms(nas_ctx *ctx);
@@ -743,18 +791,22 @@ int score_range(nas_ctx *ctx, Timer &tm, int p_lo, int p_hi, hipStream_t st = nu
     // longer needed as a gap for them (with the 256 x 256 tile and unmasked
     // streams each of them had waited ~100 us for a cost workgroup to drain:
     // profiles/r03_g8_timeline_before.txt, r03_ab_fuse_shard.txt)
-    const bool fuse = ctx->world == 1 || wide_ok(ctx);
+    // With node selectors / taints uploaded neither the fused fit nor the wide
+    // tile (which cannot read a mask) knows eligibility: the constrained k_fit
+    // writes the mask and the 256 x 256 tile reads it, at world 1 and on shards.
+    const nas::Elig *el = elig(ctx);
+    const bool fuse = !el && (ctx->world == 1 || wide_ok(ctx));
     const nas::FitSrc fit{cap, v.req, ctx->N, ctx->Nloc0, ctx->Nloc};
     hipEvent_t e0 = tm.fine(st);
     if (!fuse)
         HIPCK(nas::launch_fit(st, cap, ctx->N, ctx->Nloc0, ctx->Nloc, ctx->Mp, v.req, p_hi, v.Pp,
-                              p_lo, p_hi - p_lo, mask));
+                              p_lo, p_hi - p_lo, mask, nullptr, 1, nullptr, 0, el));
     hipEvent_t e1 = fuse ? e0 : tm.fine(st);
     const nas::Ovf ov = make_ovf(ctx);
     // (a pass with the cost-row cache: the main launches store every cost too)
     uint32_t *cache = ctx->cache_active && !view ? ctx->cost_cache.as<uint32_t>() : nullptr;
     HIPCK(launch_cost(ctx, st, v.Pp, pr0, np, mask, nullptr, 1, &ov, nullptr, fuse ? &fit : nullptr,
-                      false, cache));
+                      el != nullptr, cache));
     hipEvent_t e2 = tm.fine(st);
     tm.span(T_FIT, e0, e1);
     tm.span(T_COST, e1, e2);
@@ -833,7 +885,8 @@ int gathered_slot(nas_ctx *ctx, Timer &tm, hipStream_t st, int ch, int32_t *pub,
     auto *mask = ctx->mask.as<uint64_t>();
     hipEvent_t e1 = tm.fine(st);
     HIPCK(nas::launch_fit(st, ctx->cap.as<int32_t>(), ctx->N, ctx->Nloc0, ctx->Nloc, ctx->Mp,
-                          ctx->req.as<int32_t>(), R, R, 0, R, mask, &dyn, 1, idx, ctx->Pp));
+                          ctx->req.as<int32_t>(), R, R, 0, R, mask, &dyn, 1, idx, ctx->Pp,
+                          elig(ctx)));
     hipEvent_t e2 = tm.fine(st);
     const nas::Ovf ov = make_ovf(ctx, idx, ctl + 1);  // view row r is pod idx[r]
     HIPCK(launch_cost(ctx, st, R, 0, 0, mask, &dyn, 1, &ov, idx));
@@ -890,7 +943,8 @@ int rescore_slot(nas_ctx *ctx, hipStream_t sc, int hi, int32_t *pub = nullptr) {
     const int B = ctx->B;  // batched: every cluster with a stop gets its own window
     auto *mask = ctx->mask.as<uint64_t>();
     HIPCK(nas::launch_fit(sc, ctx->cap.as<int32_t>(), ctx->N, ctx->Nloc0, ctx->Nloc, ctx->Mp,
-                          ctx->req.as<int32_t>(), ctx->P, ctx->Pp, 0, RESCORE_PODS, mask, &dyn, B));
+                          ctx->req.as<int32_t>(), ctx->P, ctx->Pp, 0, RESCORE_PODS, mask, &dyn, B,
+                          nullptr, 0, elig(ctx)));
     const nas::Ovf ov = make_ovf(ctx);
     HIPCK(launch_cost(ctx, sc, ctx->Pp, 0, 0, mask, &dyn, B, &ov));
     const int n_lists = ctx->Mp / nas::COST_BM;
@@ -1621,7 +1675,8 @@ void nas_destroy(nas_ctx *ctx) {
                       &ctx->g_bound, &ctx->g_gk, &ctx->g_gb, &ctx->status, &ctx->scratch,
                       &ctx->vote_part, &ctx->vote_gather, &ctx->xsend[0], &ctx->xsend[1],
                       &ctx->ovf_ptr, &ctx->ovf_m, &ctx->ovf_e, &ctx->Lr, &ctx->Lt6, &ctx->WA6,
-                      &ctx->commit_flag, &ctx->zrow, &ctx->cost_cache};
+                      &ctx->commit_flag, &ctx->zrow, &ctx->cost_cache, &ctx->node_con,
+                      &ctx->pod_con};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     if (ctx->host_status.p) (void)hipHostFree(ctx->host_status.p);
@@ -2084,6 +2139,66 @@ int nas_upload_pods(nas_ctx *ctx, const int32_t *rc, const int32_t *rm, const in
     return NAS_OK;
 }
 
+// ---- node selectors and taints (nas::Elig)
+namespace {
+// dst[0, n) = src (NULL: zeros), dst[stride, stride + n) likewise for the second word
+int upload_words(nas_ctx *ctx, DevBuf &buf, const uint64_t *w0, const uint64_t *w1, int64_t n,
+                 int64_t stride) {
+    OK(nas::ensure(ctx, buf, (size_t)2 * stride * 8));
+    HIPCK(hipMemsetAsync(buf.p, 0, (size_t)2 * stride * 8, ctx->stream));
+    if (w0)
+        HIPCK(hipMemcpyAsync(buf.p, w0, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (w1)
+        HIPCK(hipMemcpyAsync(buf.as<uint64_t>() + stride, w1, (size_t)n * 8, hipMemcpyHostToDevice,
+                             ctx->stream));
+    HIPCK(hipStreamSynchronize(ctx->stream));
+    return NAS_OK;
+}
+}  // namespace
+
+int nas_upload_node_constraints(nas_ctx *ctx, const uint64_t *labels, const uint64_t *taints,
+                                int32_t n) {
+    NAS_RANGE("nas_upload_node_constraints");
+    OK(bind(ctx));
+    if (n <= 0) return nas::fail(ctx, NAS_ERR_ARG, "nas_upload_node_constraints: n");
+    if (ctx->B > 1)
+        return nas::fail(ctx, NAS_ERR_UNSUPPORTED, "node selectors / taints with a cluster batch");
+    ctx->have_node_con = false;
+    ctx->con_zero_n = 0;
+    OK(upload_words(ctx, ctx->node_con, labels, taints, n, n));
+    ctx->have_node_con = true;
+    ctx->con_n = n;
+    ctx->scored = false;  // the lists were filtered by other words
+    return NAS_OK;
+}
+
+int nas_upload_pod_constraints(nas_ctx *ctx, const uint64_t *require, const uint64_t *tolerate,
+                               int32_t P) {
+    NAS_RANGE("nas_upload_pod_constraints");
+    OK(bind(ctx));
+    if (P <= 0) return nas::fail(ctx, NAS_ERR_ARG, "nas_upload_pod_constraints: P");
+    if (ctx->B > 1)
+        return nas::fail(ctx, NAS_ERR_UNSUPPORTED, "node selectors / taints with a cluster batch");
+    ctx->have_pod_con = false;
+    ctx->con_zero_Pp = 0;
+    const int64_t Pp = nas::round_up(P, nas::COST_BN);  // padded like req
+    OK(upload_words(ctx, ctx->pod_con, require, tolerate, P, Pp));
+    ctx->have_pod_con = true;
+    ctx->con_P = P;
+    ctx->con_Pp = (int32_t)Pp;
+    ctx->scored = false;
+    return NAS_OK;
+}
+
+int nas_clear_constraints(nas_ctx *ctx) {
+    NAS_RANGE("nas_clear_constraints");
+    OK(bind(ctx));
+    if (constrained(ctx)) ctx->scored = false;
+    ctx->have_node_con = ctx->have_pod_con = false;
+    ctx->con_zero_n = ctx->con_zero_Pp = 0;
+    return NAS_OK;
+}
+
 // dtype here is the COMPUTE dtype (NAS_DT_I8 for int8 / int32 traffic)
 static int traffic_common(nas_ctx *ctx, int32_t dtype, int32_t P, int32_t n) {
     if (P <= 0 || n <= 0 || !valid_dtype(dtype))
@@ -2322,12 +2437,14 @@ int nas_filter(nas_ctx *ctx, uint64_t *mask_out) {
         return nas::fail(ctx, NAS_ERR_STATE, "nas_filter needs capacity and pods");
     if (ctx->cap_n != ctx->N || ctx->req_P != ctx->P)
         return nas::fail(ctx, NAS_ERR_STATE, "nas_filter: capacity/pods do not match the geometry");
+    OK(check_constraints(ctx, ctx->N, ctx->P));
     OK(alloc_extended(ctx));
+    OK(prepare_constraints(ctx));
     Timer tm(ctx);
     hipEvent_t a = tm.mark();
     HIPCK(nas::launch_fit(ctx->stream, ctx->cap.as<int32_t>(), ctx->N, ctx->Nloc0, ctx->Nloc,
                           ctx->Mp, ctx->req.as<int32_t>(), ctx->P, ctx->Pp, 0, ctx->P,
-                          ctx->mask.as<uint64_t>()));
+                          ctx->mask.as<uint64_t>(), nullptr, 1, nullptr, 0, elig(ctx)));
     hipEvent_t b = tm.mark();
     if (mask_out) {
         const int chunks = (ctx->Nloc + 63) / 64;
@@ -2348,6 +2465,7 @@ int nas_score(nas_ctx *ctx) {
     OK(prepare_ovf(ctx));
     OK(prepare_split(ctx));
     OK(prepare_zrow(ctx));
+    OK(prepare_constraints(ctx));
     std::memset(&ctx->timings, 0, sizeof(ctx->timings));
     Timer tm(ctx);
     if (ctx->B > 1) OK(score_batch(ctx, tm));
@@ -2408,6 +2526,7 @@ int nas_place(nas_ctx *ctx, int32_t *node_out, float *cost_out, int64_t *int_sco
     OK(prepare_ovf(ctx));
     OK(prepare_split(ctx));
     OK(prepare_zrow(ctx));
+    OK(prepare_constraints(ctx));
     std::memset(&ctx->timings, 0, sizeof(ctx->timings));
     Timer tm(ctx);
     if (ctx->B > 1) return place_batch(ctx, tm, node_out, cost_out, int_score_out);
@@ -2430,7 +2549,11 @@ int nas_place(nas_ctx *ctx, int32_t *node_out, float *cost_out, int64_t *int_sco
     const bool herd_shape = !has_coll(ctx) &&
                             (ctx->opt_herd_plan == 1 ||
                              (ctx->opt_herd_plan == 2 && ctx->herd_P == P && ctx->herd_N == N));
-    if (ctx->opt_cost_cache != 0) {
+    // (not with node selectors / taints: k_rescore_cached rebuilds lists from
+    // cached rows against capacity alone.  The constraints are replicated, so
+    // every rank of a communicator decides alike; the slots recompute through
+    // the constrained k_fit, whatever NAS_OPT_COST_CACHE says)
+    if (ctx->opt_cost_cache != 0 && !constrained(ctx)) {
         const bool herd = ctx->slot_hint_P == P && ctx->slot_hint_N == N &&
                           ctx->last_rescore_rounds >= CACHE_MIN_ROUNDS;
         const size_t bytes = (size_t)ctx->Pp * ctx->Mp * 4;
@@ -2836,6 +2959,7 @@ int nas_score_range(nas_ctx *ctx, int32_t p_lo, int32_t p_hi) {
     OK(prepare_ovf(ctx));
     OK(prepare_split(ctx));
     OK(prepare_zrow(ctx));
+    OK(prepare_constraints(ctx));
     std::memset(&ctx->timings, 0, sizeof(ctx->timings));
     Timer tm(ctx);
     OK(score_range(ctx, tm, p_lo, p_hi));
@@ -3451,6 +3575,10 @@ int nas_set_batch(nas_ctx *ctx, int32_t n_clusters) {
         return nas::fail(ctx, NAS_ERR_STATE, "nas_set_batch must precede the extended uploads");
     if (ctx->world > 1 && n_clusters > 1)
         return nas::fail(ctx, NAS_ERR_UNSUPPORTED, "node shards of a cluster batch");
+    if (n_clusters > 1 && constrained(ctx))
+        return nas::fail(ctx, NAS_ERR_UNSUPPORTED,
+                         "a cluster batch with node selectors / taints uploaded "
+                         "(nas_clear_constraints first)");
     ctx->B = n_clusters;
     return NAS_OK;
 }

@@ -67,6 +67,19 @@ struct FitSrc {
     int nloc = 0;                  // valid local nodes
 };
 
+// Per-pod node eligibility (nas_upload_node_constraints / _pod_constraints):
+// eligible(p, n) <=> (labels[n] & require[p]) == require[p] and
+// (taints[n] & ~tolerate[p]) == 0.  The node words cover the whole cluster
+// ([N], replicated on every rank like capacity), the pod words the main pod
+// array ([Pp], padded like req); k_fit decides "fits" as eligible and the
+// three resources (launch_fit's `el`).
+struct Elig {
+    const uint64_t *labels = nullptr;    // [N]
+    const uint64_t *taints = nullptr;    // [N]
+    const uint64_t *require = nullptr;   // [Pp]
+    const uint64_t *tolerate = nullptr;  // [Pp]
+};
+
 struct Ovf {
     const int32_t *ptr = nullptr;  // [B * Pp + 1] absolute offsets (nullptr: no entries)
     const int32_t *m = nullptr;
@@ -180,6 +193,15 @@ struct nas_ctx {
     nas::DevBuf zrow;
     bool zrow_valid = false;
     bool L_finite = true;
+    // node selectors and taints (nas::Elig): node_con = labels [con_n] | taints
+    // [con_n], pod_con = require [con_Pp] | tolerate [con_Pp].  A side never
+    // uploaded counts as all zero: prepare_constraints fills it (zero_n /
+    // zero_Pp: the size it was zeroed for) before a pass reads `elig`.
+    nas::DevBuf node_con, pod_con;
+    bool have_node_con = false, have_pod_con = false;
+    int32_t con_n = 0, con_P = 0, con_Pp = 0;
+    int32_t con_zero_n = 0, con_zero_Pp = 0;
+    nas::Elig elig;
     bool synth_valid = false;   // inputs came from nas_synth_cluster(synth_seed)
     uint64_t synth_seed = 0;
     int32_t synth_profile = 0;  // the profile the synthetic inputs were generated with
@@ -285,7 +307,9 @@ constexpr int MERGE_DST_WINDOW = 2;  // k_merge destination indexed from the win
 hipError_t launch_fit(hipStream_t st, const int32_t *cap, int N, int n0, int nloc, int Mp,
                       const int32_t *req, int P, int Pp, int p0, int np, uint64_t *mask,
                       const Dyn *dyn = nullptr, int batch = 1, const int32_t *rowmap = nullptr,
-                      int req_stride = 0);
+                      int req_stride = 0, const Elig *el = nullptr);
+// el (batch 1): the constrained kernels -- pod p's words are el->require[p] /
+// el->tolerate[p] of the main pod array (a view's row q: pod rowmap[q])
 
 // pods per tile of the wide cost kernel for this (compute) dtype when it is
 // built in (384), else COST_BN

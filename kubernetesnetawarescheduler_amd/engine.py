@@ -327,6 +327,34 @@ class Engine:
         self._ck(self._L.nas_upload_pods(self._h, *[ptr(c) for c in cols], req.shape[-2]))
         self.n_pods = req.shape[-2]
 
+    # node selectors and taints (include/nas.h): eligible(p, n) <=>
+    # (labels[n] & require[p]) == require[p] and (taints[n] & ~tolerate[p]) == 0
+    @staticmethod
+    def _words(a, b, what):
+        a = None if a is None else as_c(a, np.uint64).reshape(-1)
+        b = None if b is None else as_c(b, np.uint64).reshape(-1)
+        if a is not None and b is not None and a.shape != b.shape:
+            raise ValueError(f"{what}: the two word arrays differ in length")
+        return a, b
+
+    def upload_node_constraints(self, labels=None, taints=None):
+        """uint64 label / taint words per node (None: all zero); with both
+        None the length is the uploaded node count."""
+        labels, taints = self._words(labels, taints, "upload_node_constraints")
+        n = next((a.shape[0] for a in (labels, taints) if a is not None), self.n_nodes)
+        self._ck(self._L.nas_upload_node_constraints(self._h, ptr(labels), ptr(taints), n))
+
+    def upload_pod_constraints(self, require=None, tolerate=None):
+        """uint64 require / tolerate words per pod (None: all zero); with both
+        None the length is the uploaded pod count."""
+        require, tolerate = self._words(require, tolerate, "upload_pod_constraints")
+        P = next((a.shape[0] for a in (require, tolerate) if a is not None), self.n_pods)
+        self._ck(self._L.nas_upload_pod_constraints(self._h, ptr(require), ptr(tolerate), P))
+
+    def clear_constraints(self):
+        """Back to the resource fit only."""
+        self._ck(self._L.nas_clear_constraints(self._h))
+
     @staticmethod
     def _int_traffic(a):
         """Integer traffic for int8 scoring: an int8 array as is (NAS_DT_I8),

@@ -354,6 +354,57 @@ int nas_host_schedule_batch(nas_host_sched *s, int32_t max_pods, nas_host_outcom
     })
 }
 
+namespace {
+// n strings (none NULL) -> vector; false on a bad argument
+bool strings_of(const char *const *v, int32_t n, std::vector<std::string> &out) {
+    if (n < 0 || (n > 0 && !v)) return false;
+    for (int32_t i = 0; i < n; ++i) {
+        if (!v[i]) return false;
+        out.emplace_back(v[i]);
+    }
+    return true;
+}
+}  // namespace
+
+int nas_host_set_node_constraints(nas_host_sched *s, const char *node, const char *const *labels,
+                                  int32_t n_labels, const char *const *taints, int32_t n_taints) {
+    if (!s || !node) return NAS_ERR_ARG;
+    GUARD(s, {
+        std::vector<std::string> l;
+        std::vector<std::string> t;
+        if (!strings_of(labels, n_labels, l) || !strings_of(taints, n_taints, t)) return NAS_ERR_ARG;
+        s->s->set_node_constraints(node, std::move(l), std::move(t));
+        return NAS_OK;
+    })
+}
+
+int nas_host_set_pod_constraints(nas_host_sched *s, const char *ns_name,
+                                 const char *const *node_selector, int32_t n_sel,
+                                 const char *const *tolerations, int32_t n_tol) {
+    if (!s || !ns_name) return NAS_ERR_ARG;
+    GUARD(s, {
+        std::vector<std::string> l;
+        std::vector<std::string> t;
+        if (!strings_of(node_selector, n_sel, l) || !strings_of(tolerations, n_tol, t))
+            return NAS_ERR_ARG;
+        s->s->set_pod_constraints(ns_name, std::move(l), std::move(t));
+        return NAS_OK;
+    })
+}
+
+int nas_host_intern_bits(const char *const *universe, int32_t n_universe, const char *const *have,
+                         int32_t n_have, uint64_t *bits_out) {
+    if (!bits_out || n_universe > 64) return NAS_ERR_ARG;
+    try {
+        std::vector<std::string> u, h;
+        if (!strings_of(universe, n_universe, u) || !strings_of(have, n_have, h)) return NAS_ERR_ARG;
+        *bits_out = intern_bits(u, h);
+    } catch (...) {
+        return NAS_ERR_STATE;
+    }
+    return NAS_OK;
+}
+
 int nas_host_place_pending(nas_host_sched *s, nas_host_outcome *out, int32_t *n_out) {
     if (!s || !out || !n_out) return NAS_ERR_ARG;
     GUARD(s, {

@@ -28,6 +28,16 @@ std::vector<Endpoint> reference_topology() {
             {"raspiworker3", "http://192.168.1.134:9100/metrics"}};
 }
 
+uint64_t intern_bits(const std::vector<std::string> &universe, const std::vector<std::string> &have) {
+    if (universe.size() > 64)
+        throw std::invalid_argument("a bit universe of " + std::to_string(universe.size()) +
+                                    " strings (64 at most)");
+    uint64_t bits = 0;
+    for (size_t i = 0; i < universe.size(); ++i)
+        if (std::find(have.begin(), have.end(), universe[i]) != have.end()) bits |= 1ull << i;
+    return bits;
+}
+
 CustomScheduler::CustomScheduler(nas_ctx *ctx, ClusterApi &api, MetricsSource &src, MapOrder &order)
     : ctx_(ctx), api_(api), src_(src), order_(order), topo_(reference_topology()) {}
 
@@ -256,11 +266,58 @@ std::vector<std::pair<Pod, Outcome>> CustomScheduler::place_pending() {
                                        lat_f32_ ? NAS_DT_F32 : NAS_DT_I32, P, n,
                                        (int64_t)peer_node.size()),
           "nas_upload_traffic_csr");
+    // node selectors and taints -> bits, for this call: a label counts only if
+    // a pending pod selects it (whether or not a listed node carries it), a
+    // taint only if a listed node carries it
+    static const StringSets kNone;
+    auto con_of = [](const std::map<std::string, StringSets> &m, const std::string &k) -> const StringSets & {
+        auto it = m.find(k);
+        return it == m.end() ? kNone : it->second;
+    };
+    std::vector<std::string> label_u, taint_u;
+    auto add = [](std::vector<std::string> &u, const std::string &v) {
+        if (std::find(u.begin(), u.end(), v) == u.end()) u.push_back(v);
+    };
+    for (int p = 0; p < P; ++p)
+        for (const std::string &l : con_of(pod_con_, pods[p].ns + "/" + pods[p].name).first) add(label_u, l);
+    for (int i = 0; i < n; ++i)
+        for (const std::string &t : con_of(node_con_, nodes[i]).second) add(taint_u, t);
+    if (label_u.size() > 64)
+        throw std::runtime_error(std::to_string(label_u.size()) +
+                                 " distinct node-selector labels among the pending pods (64 at most)");
+    if (taint_u.size() > 64)
+        throw std::runtime_error(std::to_string(taint_u.size()) +
+                                 " distinct taints among the listed nodes (64 at most)");
+    std::vector<uint64_t> labels(n, 0), taints(n, 0), require(P, 0), tolerate(P, 0);
+    const bool con = !label_u.empty() || !taint_u.empty();
+    if (con) {
+        for (int i = 0; i < n; ++i) {
+            const StringSets &c = con_of(node_con_, nodes[i]);
+            labels[i] = intern_bits(label_u, c.first);
+            taints[i] = intern_bits(taint_u, c.second);
+        }
+        for (int p = 0; p < P; ++p) {
+            const StringSets &c = con_of(pod_con_, pods[p].ns + "/" + pods[p].name);
+            require[p] = intern_bits(label_u, c.first);
+            tolerate[p] = intern_bits(taint_u, c.second);
+        }
+        check(ctx_, nas_upload_node_constraints(ctx_, labels.data(), taints.data(), n),
+              "nas_upload_node_constraints");
+        check(ctx_, nas_upload_pod_constraints(ctx_, require.data(), tolerate.data(), P),
+              "nas_upload_pod_constraints");
+    } else {
+        check(ctx_, nas_clear_constraints(ctx_), "nas_clear_constraints");
+    }
     std::vector<int32_t> node_out(P);
     check(ctx_, nas_place(ctx_, node_out.data(), nullptr, nullptr), "nas_place");
     for (int p = 0; p < P; ++p) {
         if (node_out[p] < 0) {
-            out.push_back({pods[p], {Outcome::UNSCHEDULABLE, "", "no node fits the pod's requests"}});
+            bool any = false;  // some node is eligible: the requests did not fit
+            for (int i = 0; i < n && !any; ++i)
+                any = (labels[i] & require[p]) == require[p] && (taints[i] & ~tolerate[p]) == 0;
+            out.push_back({pods[p], {Outcome::UNSCHEDULABLE, "",
+                                     any ? "no node fits the pod's requests"
+                                         : "no node matches the pod's node selector and tolerations"}});
             continue;
         }
         out.push_back({pods[p], bind_and_event(pods[p], nodes[node_out[p]])});

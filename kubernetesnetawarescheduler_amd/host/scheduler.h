@@ -20,7 +20,8 @@
 //   schedule_batch: one metrics scrape for a batch of pods, one GPU call;
 //   place_pending: fit + network cost + greedy commit for every queued pod
 //   (nas_place) against node capacities, a pairwise latency matrix and the
-//   pods' traffic to already-bound peers.
+//   pods' traffic to already-bound peers, honouring node selectors and
+//   taints (set_node_constraints / set_pod_constraints).
 #pragma once
 
 #include <cstdint>
@@ -85,6 +86,10 @@ struct Endpoint {
 };
 std::vector<Endpoint> reference_topology();  // :275-279
 
+// bit i <=> universe[i] is among `have` (strings outside the universe are
+// ignored); throws std::invalid_argument for more than 64 universe strings
+uint64_t intern_bits(const std::vector<std::string> &universe, const std::vector<std::string> &have);
+
 struct Outcome {
     enum Kind { BOUND, NO_POD, LIST_ERROR, BIND_ERROR, EVENT_ERROR, PANIC, UNSCHEDULABLE } kind;
     std::string node, message;
@@ -121,6 +126,17 @@ public:
     void set_latency(const std::vector<std::string> &names, const std::vector<int8_t> &L);
     void set_latency_f32(const std::vector<std::string> &names, const std::vector<float> &L);
 
+    // node selectors and taints for place_pending (exact string match): a
+    // node's labels / taints, a pod's ("namespace/name") selector / tolerations
+    void set_node_constraints(const std::string &node, std::vector<std::string> labels,
+                              std::vector<std::string> taints) {
+        node_con_[node] = {std::move(labels), std::move(taints)};
+    }
+    void set_pod_constraints(const std::string &ns_name, std::vector<std::string> selector,
+                             std::vector<std::string> tolerations) {
+        pod_con_[ns_name] = {std::move(selector), std::move(tolerations)};
+    }
+
     void set_topology(std::vector<Endpoint> t) { topo_ = std::move(t); }
     // replaces the reference's node -> report map (:505-510) entry by entry
     void add_iperf_path(const std::string &node, const std::string &path) {
@@ -152,6 +168,9 @@ private:
     std::vector<int8_t> lat_;
     std::vector<float> lat_f_;
     bool lat_f32_ = false;  // place_pending on lat_f_ (NAS_DT_F32)
+    // first: labels / node selector, second: taints / tolerations
+    using StringSets = std::pair<std::vector<std::string>, std::vector<std::string>>;
+    std::map<std::string, StringSets> node_con_, pod_con_;
 };
 
 }  // namespace nas_host

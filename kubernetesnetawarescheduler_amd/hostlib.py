@@ -85,6 +85,12 @@ SIGNATURES = {
     "nas_host_schedule_one": (_c.c_int, [_P, _c.POINTER(HostOutcome)]),
     "nas_host_schedule_batch": (_c.c_int, [_P, _c.c_int32, _c.POINTER(HostOutcome), _I32P]),
     "nas_host_place_pending": (_c.c_int, [_P, _c.POINTER(HostOutcome), _I32P]),
+    "nas_host_set_node_constraints": (_c.c_int, [_P, _CS, _c.POINTER(_CS), _c.c_int32,
+                                                 _c.POINTER(_CS), _c.c_int32]),
+    "nas_host_set_pod_constraints": (_c.c_int, [_P, _CS, _c.POINTER(_CS), _c.c_int32,
+                                                _c.POINTER(_CS), _c.c_int32]),
+    "nas_host_intern_bits": (_c.c_int, [_c.POINTER(_CS), _c.c_int32, _c.POINTER(_CS), _c.c_int32,
+                                        _c.POINTER(_c.c_uint64)]),
 }
 
 _HL = None
@@ -185,6 +191,23 @@ def latency_matrix(reports, us=False):
     if rc != 0:
         raise NasError(rc, "nas_host_latency_matrix")
     return L
+
+
+def _strs(xs):
+    xs = [_b(x) for x in xs]
+    return (_CS * max(1, len(xs)))(*xs), len(xs)
+
+
+def intern_bits(universe, have):
+    """Bit i <=> universe[i] is among `have` (nas_host_intern_bits: strings
+    outside the universe are ignored, more than 64 universe strings raise)."""
+    u, nu = _strs(universe)
+    h, nh = _strs(have)
+    bits = _c.c_uint64()
+    rc = hostlib().nas_host_intern_bits(u, nu, h, nh, _c.byref(bits))
+    if rc != 0:
+        raise NasError(rc, f"nas_host_intern_bits: a universe of {nu} strings")
+    return bits.value
 
 
 class GoPanicError(RuntimeError):
@@ -321,6 +344,18 @@ class HostScheduler:
         a = (_CS * n)(*[_b(x) for x in names])
         fn = self._L.nas_host_set_latency_f32 if f32 else self._L.nas_host_set_latency
         self._ck(fn(self._h, a, L.ctypes.data_as(_c.c_void_p), n))
+
+    def set_node_constraints(self, node, labels=(), taints=()):
+        """A node's labels ("key=value") and taints ("key=value:NoSchedule")."""
+        l, nl = _strs(labels)
+        t, nt = _strs(taints)
+        self._ck(self._L.nas_host_set_node_constraints(self._h, _b(node), l, nl, t, nt))
+
+    def set_pod_constraints(self, ns_name, node_selector=(), tolerations=()):
+        """A pod's ("namespace/name") node selector and tolerations."""
+        l, nl = _strs(node_selector)
+        t, nt = _strs(tolerations)
+        self._ck(self._L.nas_host_set_pod_constraints(self._h, _b(ns_name), l, nl, t, nt))
 
     def enqueue(self, ns, name, uid="", scheduler_name="netAwareScheduler", node_name="",
                 cpu_milli=0, mem_kib=0, peers=()):

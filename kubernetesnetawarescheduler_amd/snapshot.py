@@ -26,6 +26,10 @@ import numpy as np
 PLACE_FORMAT = "nas-place-problem/1"
 VOTE_FORMAT = "nas-vote-problem/1"
 DTYPES = ("i8", "bf16", "f32")
+# optional keys of a dense placement file: node selectors and taints as uint64
+# words (Engine.upload_node_constraints / upload_pod_constraints); files
+# without them replay as resource fit only
+CONSTRAINT_KEYS = ("labels", "taints", "require", "tolerate")
 
 
 def _meta(d):
@@ -36,15 +40,22 @@ def _unmeta(a):
     return json.loads(bytes(np.asarray(a, np.uint8)).decode())
 
 
-def save_place(path, L, free, req, WA, dtype="i8", meta=None):
+def save_place(path, L, free, req, WA, dtype="i8", meta=None, constraints=None):
     """Dense network-aware problem.  WA: integer traffic (int8 scoring, any
-    int32), uint16 bf16 bits, or float32, as `Engine.upload_traffic` takes."""
+    int32), uint16 bf16 bits, or float32, as `Engine.upload_traffic` takes.
+    constraints: optional dict with any of CONSTRAINT_KEYS (uint64 words)."""
     if dtype not in DTYPES:
         raise ValueError(f"dtype {dtype!r}")
+    extra = {}
+    for k, v in (constraints or {}).items():
+        if k not in CONSTRAINT_KEYS:
+            raise ValueError(f"constraints key {k!r}")
+        if v is not None:
+            extra[k] = np.ascontiguousarray(v, np.uint64)
     np.savez(path, format=np.array(PLACE_FORMAT), kind=np.array("dense"), dtype=np.array(dtype),
              L=np.ascontiguousarray(L), free=np.ascontiguousarray(free, np.int32),
              req=np.ascontiguousarray(req, np.int32), WA=np.ascontiguousarray(WA),
-             meta=_meta(meta or {}))
+             meta=_meta(meta or {}), **extra)
 
 
 def save_place_synth(path, seed, n_nodes, P, dtype="i8", peers=8, meta=None):
@@ -78,16 +89,18 @@ def load(path):
     return out
 
 
-def capture_place(engine, path, rows_per_read=4096, meta=None):
+def capture_place(engine, path, rows_per_read=4096, meta=None, constraints=None):
     """The engine's uploaded network-aware inputs (one cluster, before a
-    pass moves its capacity) into a dense replay file."""
+    pass moves its capacity) into a dense replay file.  The engine keeps no
+    host copy of its constraint words: pass the arrays that were uploaded
+    (`constraints`, as save_place takes them) to carry them in the file."""
     P, N = engine.n_pods, engine.n_nodes
     _, L, free, req = engine.read_inputs(0, 0, want_L=True)
     parts = []
     for p0 in range(0, P, rows_per_read):
         WA, _, _, _ = engine.read_inputs(p0, min(rows_per_read, P - p0), want_L=False)
         parts.append(WA)
-    save_place(path, L, free, req, np.concatenate(parts, 0), engine.dtype, meta)
+    save_place(path, L, free, req, np.concatenate(parts, 0), engine.dtype, meta, constraints)
 
 
 def replay_place(engine, path, want_cost=True):
@@ -104,6 +117,13 @@ def replay_place(engine, path, want_cost=True):
         engine.upload_capacity(f["free"])
         engine.upload_pods(f["req"])
         engine.upload_traffic(f["WA"], dt)
+    # the file's constraint words, or none: a file without them must not
+    # inherit what the engine placed before
+    engine.clear_constraints()
+    if "labels" in f or "taints" in f:
+        engine.upload_node_constraints(f.get("labels"), f.get("taints"))
+    if "require" in f or "tolerate" in f:
+        engine.upload_pod_constraints(f.get("require"), f.get("tolerate"))
     return engine.place(want_cost=want_cost)
 
 

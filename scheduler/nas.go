@@ -201,6 +201,51 @@ func (e *nasEngine) uploadNetwork(names []string, latencyUs []float32, cpuMilli,
 	return nasErr(e.ctx, rc, "nas_upload_capacity")
 }
 
+// uploadNodeConstraints / uploadPodConstraints: node selectors and taints as
+// 64-bit words (the host interns the strings to bits, INTEGRATION.md): pod p
+// may go to node n only if labels[n] has every bit of require[p] and
+// taints[n] has no bit outside tolerate[p].  nil means all zero; the words
+// stay until re-uploaded or clearConstraints.  Call after uploadNetwork (node
+// words) and before placeBatch (pod words, same pod order).
+func (e *nasEngine) uploadNodeConstraints(labels, taints []uint64) error {
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	n := len(e.names)
+	if (labels != nil && len(labels) != n) || (taints != nil && len(taints) != n) || n == 0 {
+		return errors.New("uploadNodeConstraints: sizes")
+	}
+	var l, t *C.uint64_t
+	if labels != nil {
+		l = (*C.uint64_t)(&labels[0])
+	}
+	if taints != nil {
+		t = (*C.uint64_t)(&taints[0])
+	}
+	return nasErr(e.ctx, C.nas_upload_node_constraints(e.ctx, l, t, C.int32_t(n)), "nas_upload_node_constraints")
+}
+
+func (e *nasEngine) uploadPodConstraints(require, tolerate []uint64, P int) error {
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	if (require != nil && len(require) != P) || (tolerate != nil && len(tolerate) != P) || P == 0 {
+		return errors.New("uploadPodConstraints: sizes")
+	}
+	var r, t *C.uint64_t
+	if require != nil {
+		r = (*C.uint64_t)(&require[0])
+	}
+	if tolerate != nil {
+		t = (*C.uint64_t)(&tolerate[0])
+	}
+	return nasErr(e.ctx, C.nas_upload_pod_constraints(e.ctx, r, t, C.int32_t(P)), "nas_upload_pod_constraints")
+}
+
+func (e *nasEngine) clearConstraints() error {
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	return nasErr(e.ctx, C.nas_clear_constraints(e.ctx), "nas_clear_constraints")
+}
+
 // placeBatch is the network-aware path: pods drained from podQueue (:129) in
 // arrival order, each with its requests and its traffic (MB, fp32) to
 // already-bound peers as CSR -- peerNode[rowPtr[p]:rowPtr[p+1]] is the node
