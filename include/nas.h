@@ -58,8 +58,13 @@ extern "C" {
 #define NAS_DT_F32 4  /* fp32 latency and traffic as measured (no quantisation): each
                        * operand split into three bf16 planes (x = h + m + l), the
                        * products to 2^-24 relative on the bf16 MFMA (six terms),
-                       * fp32 accumulation -- costs within 1e-5 relative of an fp64
-                       * sum */
+                       * fp32 accumulation.  Accuracy: |cost - exact| <= 1e-5 *
+                       * sum_m |WA[p,m] * L[m,n]|, exact = the fp64 sum -- 1e-5 of
+                       * the cost's own magnitude when nothing cancels (operands of
+                       * one sign); with operands of both signs the terms cancel
+                       * and the error relative to the cost itself is unbounded.
+                       * Operands whose plane products and partial sums are all
+                       * exact in fp32 give the exact cost. */
 
 /* winner slots returned by nas_score_reference (order of scheduler.go:360-365) */
 #define NAS_W_CPU 0

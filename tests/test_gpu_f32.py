@@ -4,7 +4,10 @@ bf16 planes and contracted on the bf16 MFMA over a six-fold K (products to
 2^-24 relative) with fp32 accumulation.  The north star's bar for raw
 floating-point costs is 1e-5 relative to an fp64 sum (REL_TOL below); the
 chosen nodes must equal the fp64 sequential oracle's wherever the cost gap at
-a pod's turn exceeds that tolerance."""
+a pod's turn exceeds that tolerance.  With operands of both signs the terms
+cancel and the bar is REL_TOL of sum_m |WA L| (the same thing while nothing
+cancels); operands on which the path must be exact are in
+test_gpu_float_exact.py."""
 import numpy as np
 import pytest
 
@@ -54,6 +57,27 @@ def test_f32_candidates_within_tolerance(engine, P, N):
     assert rel[use].max() <= REL_TOL, rel[use].max()
     # the GPU's j-th candidate is a true j-th best up to the tolerance
     assert (np.abs(exact - wc) <= REL_TOL * np.abs(wc))[use].all()
+
+
+@pytest.mark.parametrize("P,N", [(300, 257), (512, 1024)])
+def test_f32_signed_wide_range_within_abs_sum(engine, P, N):
+    """Operands of both signs over 8 and 11 decades: terms cancel, so the
+    error is measured against S = sum_m |WA L| (include/nas.h NAS_DT_F32), not
+    against the cost -- for the positive operands above S is the cost, and
+    this is the same REL_TOL."""
+    import float_cases as fc
+    from util import cluster
+    rng = np.random.default_rng(1000 * P + N)
+    WA, L = fc.measured_operands(rng, P, N)
+    _, _, free, req = cluster(rng, P, N, cap_scale=1.0)
+    upload(engine, WA, L, free, req)
+    engine.score()
+    node, _, cf, cnt, _ = engine.candidates()
+    cost = oracle.cost(WA, L, "f32")
+    assert (cost < 0).any() and (cost > 0).any()
+    S = np.abs(WA.astype(np.float64)) @ np.abs(L.astype(np.float64))
+    _, wc, wcnt = oracle.topk(cost, oracle.fit_mask(req, free), 8)
+    fc.check_within_abs_sum(node, cf, cnt, cost, wc, wcnt, S, REL_TOL)
 
 
 def _greedy_within_tol(node, cf, cost, req, free):

@@ -178,6 +178,27 @@ def test_cost_bf16_random_within_tolerance(engine):
     assert (np.abs(exact - wc) <= REL_TOL * np.abs(wc))[usable].all()
 
 
+@pytest.mark.parametrize("P,N", [(300, 257), (512, 1024)])
+def test_cost_bf16_signed_wide_range_within_abs_sum(engine, P, N):
+    """The twin of the test above on operands of both signs over many decades
+    (float_cases.measured_operands, rounded to bf16): terms cancel, so the
+    error is measured against sum_m |WA L| -- the cost's own magnitude above,
+    where nothing cancels -- at the same REL_TOL."""
+    import float_cases as fc
+    from util import f32_to_bf16_bits
+    rng = np.random.default_rng(1000 * P + N)
+    WA, L = (f32_to_bf16_bits(x) for x in fc.measured_operands(rng, P, N))
+    _, _, free, req = cluster(rng, P, N, cap_scale=1.0)
+    upload(engine, WA, L, free, req, "bf16")
+    engine.score()
+    node, _, cf, cnt, _ = engine.candidates()
+    cost = oracle.cost(WA, L, "bf16")
+    assert (cost < 0).any() and (cost > 0).any()
+    S = np.abs(bf16_bits_to_f64(WA)) @ np.abs(bf16_bits_to_f64(L))
+    _, wc, wcnt = oracle.topk(cost, oracle.fit_mask(req, free), 8)
+    fc.check_within_abs_sum(node, cf, cnt, cost, wc, wcnt, S, REL_TOL)
+
+
 def test_csr_traffic_matches_dense(engine):
     rng = np.random.default_rng(8)
     P, N = 600, 300
