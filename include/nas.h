@@ -288,7 +288,9 @@ int nas_vote_merge(nas_ctx *ctx, const nas_vote_partial *parts, int32_t n_parts,
 /* Dense latency matrix L[m * n + j] = latency from node m to node j,
  * uploaded once (dtype NAS_DT_I8, NAS_DT_BF16 or NAS_DT_F32).  Integer scores are exact
  * int32: nas_place / nas_score return NAS_ERR_UNSUPPORTED when some pod's
- * sum_m |WA[p,m]| * max|L| exceeds INT32_MAX. */
+ * sum_m |WA[p,m]| * max|L| exceeds INT32_MAX - 1.  (Costs are ranked as the
+ * 32-bit key word cost ^ 2^31; the word of cost INT32_MAX, all-ones, is reserved
+ * for "does not fit", so the largest accepted bound is INT32_MAX - 1.) */
 int nas_upload_latency(nas_ctx *ctx, const void *L, int32_t dtype, int32_t n);
 
 /* Free capacity per node; also resets the working capacity nas_place uses. */

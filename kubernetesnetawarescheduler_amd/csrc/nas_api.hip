@@ -477,12 +477,14 @@ int check_extended(nas_ctx *ctx) {
         return nas::fail(ctx, NAS_ERR_STATE, "re-upload latency and traffic after resizing");
     if (ctx->world > 1 && !has_coll(ctx) && !ctx->virtual_shard)
         return nas::fail(ctx, NAS_ERR_STATE, "node shard without a communicator");
-    // int8 path: exact int32 costs need sum_m |WA[p,m]| * |L[m,n]| <= INT32_MAX
-    if (ctx->dtype == NAS_DT_I8 && ctx->wa_abs_row_max * (int64_t)ctx->L_abs_max > 0x7fffffffLL)
+    // int8 path: exact int32 costs need sum_m |WA[p,m]| * |L[m,n]| < INT32_MAX (the key
+    // word of cost INT32_MAX is all-ones, which Top4 and the cost-row cache read as
+    // "does not fit")
+    if (ctx->dtype == NAS_DT_I8 && ctx->wa_abs_row_max * (int64_t)ctx->L_abs_max >= 0x7fffffffLL)
         return nas::fail(ctx, NAS_ERR_UNSUPPORTED,
                          "int8 path: a pod's sum_m |WA[p,m]| * max|L| = " +
                              std::to_string(ctx->wa_abs_row_max) + " * " +
-                             std::to_string(ctx->L_abs_max) + " exceeds int32");
+                             std::to_string(ctx->L_abs_max) + " exceeds INT32_MAX - 1");
     return check_constraints(ctx, ctx->N, ctx->P);
 }
 
