@@ -153,7 +153,10 @@ __device__ __forceinline__ unsigned umed3(unsigned a, unsigned b, unsigned c) {
 // RMAP: a gathered rescore view -- view row q's traffic is WA row rowmap[q]
 // (read in place by the LDS-DMA source addresses; rows past the view's count
 // read its last row and are never merged)
-template <int DT, bool RMAP, int NWN, bool FUSE>
+// OSTG (the wide int8 tile): the tile's overflow entries are staged through
+// LDS (seed_ovf_staged; the launcher picks it when no tile of the traffic
+// holds more than OVF_STAGE_ENTRIES)
+template <int DT, bool RMAP, int NWN, bool FUSE, bool OSTG = false>
 __global__ void __launch_bounds__(128 * NWN, 1)
 k_cost_topk(const unsigned char *__restrict__ Lt, const unsigned char *__restrict__ WA, int Kb,
             int n_mt, int n_nt, int p0, int Pp, const u64 *__restrict__ mask,
@@ -168,6 +171,7 @@ k_cost_topk(const unsigned char *__restrict__ Lt, const unsigned char *__restric
     constexpr bool WIDE = BNK > BN;
     static_assert(!WIDE || (!RMAP && FUSE), "the wide tile serves the main pass only");
     static_assert(!FUSE || !RMAP, "the fused fit: main-range launches");
+    static_assert(!OSTG || (WIDE && DT == NAS_DT_I8), "overflow staging: the wide int8 tile");
     constexpr int STG = (BM + BNK) * BKB;    // bytes per LDS stage
     constexpr int PG = WIDE ? PG_WIDE : PG_NARROW;
     constexpr int PPWA = (BM / 8 + NW - 1) / NW;   // 1 KiB LDS-DMA pieces of A per wave per stage
@@ -424,14 +428,16 @@ k_cost_topk(const unsigned char *__restrict__ Lt, const unsigned char *__restric
     // four 32-node tiles) in one round, so an entry costs two dependent
     // loads, not eight; the two-stage pipeline runs this behind its first
     // stage's LDS-DMA (the prologue waits once for both)
-    // (the layout of rounds 1-2, inline: the wide tile, whose registers allow
-    // one tile's row dwords at a time, and the 256 x 256 launches without the
-    // fused fit -- node shards, rescore windows -- which must stay at <= 192
-    // VGPRs: a node shard's merge / all-gather / commit kernels run beside a
-    // cost workgroup only while its two waves per SIMD leave registers free
-    // (at 256 VGPRs the G = 8 rehearsal pass rose from 1.39 to 1.50 ms:
-    // profiles/r03_bisect_g8.txt))
-    constexpr bool OVF_ROUND2 = WIDE || !FUSE;
+    // (the layout of rounds 1-2, inline, one tile's row dwords at a time: the
+    // 256 x 256 launches without the fused fit -- node shards, rescore
+    // windows -- which must stay at <= 192 VGPRs: a node shard's merge /
+    // all-gather / commit kernels run beside a cost workgroup only while its
+    // two waves per SIMD leave registers free (at 256 VGPRs the G = 8
+    // rehearsal pass rose from 1.39 to 1.50 ms: profiles/r03_bisect_g8.txt);
+    // and the wide tile, whose registers allow no more, when some tile of the
+    // traffic holds more entries than the LDS scratch of seed_ovf_staged
+    // below (!OSTG))
+    constexpr bool OVF_ROUND2 = (WIDE && !OSTG) || !FUSE;
     if constexpr (OVF_ROUND2 && DT == NAS_DT_I8) {
         if (ov.ptr) {
             const int cnt_lim = ov.row_count ? *ov.row_count : 0x7fffffff;
@@ -461,8 +467,86 @@ k_cost_topk(const unsigned char *__restrict__ Lt, const unsigned char *__restric
             }
         }
     }
+    // The wide tile stages its entries through LDS, behind stage 0's LDS-DMA.
+    // A wide workgroup owns its CU, so a chain of dependent global loads in
+    // front of its first K stage is idle time of the whole CU, and the loop
+    // above costs two round trips per entry, pod group and 32-node block, one
+    // wave's longest list after the other.  The second staging image is
+    // unused until the K loop's first iteration issues stage 1; it holds, per
+    // entry of the tile, a 256-byte segment of its latency row (this tile's
+    // nodes) and its (m, e) record.  The pods of a tile are consecutive (the
+    // wide tile serves no row map: launch_cost_t), so its entries are one run
+    // [base, base + n) of the lists and slot s is entry base + s.  That makes
+    // three dependent rounds per tile whatever the lists hold: the bounds
+    // (stage 0 in flight), the records, and the row segments -- LDS-DMA, 16
+    // lanes per entry, with a 16-byte-chunk XOR swizzle (chunk ^= slot & 15)
+    // on the SOURCE address, so that the lanes of a wave, which read the same
+    // column of different slots, spread over the banks.  Then each lane walks
+    // its two pods' slots in LDS, four row dwords at a time as above.
+    constexpr int OVF_CAP = OVF_STAGE_ENTRIES;
+    constexpr int OVF_SEG = BM;  // bytes of an entry's row segment
+    static_assert(!WIDE || (OVF_CAP % 4 == 0 && OVF_CAP <= 128 * NWN &&
+                            OVF_CAP * (OVF_SEG + 8) <= STG), "overflow staging scratch");
+    auto seed_ovf_staged = [&]() __attribute__((always_inline)) {
+        if constexpr (OSTG) {
+            if (!ov.ptr) return;
+            static_assert(!M16, "32x32 accumulator blocks");
+            unsigned char *rows = lds + STG;                                    // [CAP][SEG]
+            int2 *ent = reinterpret_cast<int2 *>(lds + STG + OVF_CAP * OVF_SEG);  // [CAP] (m, e)
+            const int r0 = p0 + nt * BNK, r1 = min(r0 + BNK, p_end);
+            const int *pp = ov.ptr + (size_t)cb * Pp;
+            const signed char *lrt = ov.Lr + (size_t)cb * ov.N * (n_mt * BM) + mt * BM;
+            const int base = __builtin_amdgcn_readfirstlane(pp[r0]);
+            // (the launcher's promise; the clamp keeps a broken one inside the scratch)
+            const int n = min(__builtin_amdgcn_readfirstlane(pp[r1]) - base, OVF_CAP);
+            if (n == 0) return;
+            // the lane's pods' slots [sb, se)
+            int sb[AN], se[AN];
+#pragma unroll
+            for (int ni = 0; ni < AN; ++ni) {
+                const int r = r0 + wn * WPODS + ni * PB + fr;
+                sb[ni] = se[ni] = 0;
+                if (r < r1) {
+                    sb[ni] = pp[r] - base;
+                    se[ni] = min(pp[r + 1] - base, n);
+                }
+            }
+            if (tid < n) ent[tid] = make_int2(ov.m[base + tid], ov.e[base + tid]);
+            __syncthreads();
+            // four slots per 1 KiB piece, lane l -> slot l / 16, chunk l % 16
+            // (slots past the last one re-read it into unused scratch)
+            for (int g = wu; 4 * g < n; g += NW) {
+                const int s = 4 * g + (lane >> 4);
+                const int m = ent[min(s, n - 1)].x;
+                glds16(lrt + (size_t)m * (n_mt * BM) + (((lane & 15) ^ (s & 15)) << 4),
+                       rows + g * 4 * OVF_SEG);
+            }
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+#pragma unroll
+            for (int ni = 0; ni < AN; ++ni)
+#pragma unroll
+                for (int mi = 0; mi < AM; ++mi)
+                    for (int s = sb[ni]; s < se[ni]; ++s) {
+                        const int e = ent[s].y;
+                        const unsigned char *row = rows + s * OVF_SEG;
+#pragma unroll
+                        for (int g = 0; g < AR / 4; ++g) {
+                            // dword wm*32 + mi*8 + 2g + fh of the segment
+                            const int ch = wm * 8 + mi * 2 + (g >> 1);
+                            const int v = *reinterpret_cast<const int *>(
+                                row + ((ch ^ (s & 15)) << 4) + (2 * (g & 1) + fh) * 4);
+#pragma unroll
+                            for (int c = 0; c < 4; ++c)
+                                acc[mi][ni][4 * g + c] += e * (int)(signed char)(v >> (8 * c));
+                        }
+                    }
+            // (the pre-loop barrier keeps stage 1 off the scratch until every
+            // wave is done with it)
+        }
+    };
     auto seed_ovf = [&]() __attribute__((always_inline)) {
-        if constexpr (!OVF_ROUND2 && DT == NAS_DT_I8) {
+        if constexpr (!OVF_ROUND2 && !WIDE && DT == NAS_DT_I8) {
             if (ov.ptr) {
                 const int cnt_lim = ov.row_count ? *ov.row_count : 0x7fffffff;
                 const signed char *lr = ov.Lr + (size_t)cb * ov.N * (n_mt * BM) + mt * BM + wm * 128 + 4 * fh;
@@ -571,6 +655,7 @@ k_cost_topk(const unsigned char *__restrict__ Lt, const unsigned char *__restric
     stageA(0, 0);
     stageB(0, 0);
     seed_ovf();
+    seed_ovf_staged();
     if constexpr (!WIDE) load_mask();
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -933,7 +1018,7 @@ k_merge(const u64 *__restrict__ keys, const u64 *__restrict__ bounds, int n_list
     dst_bound[p] = umin64(bound, a[7]);
 }
 
-template <int DT, bool RMAP, int NWN = 4, bool FUSE = (NWN == 6)>
+template <int DT, bool RMAP, int NWN = 4, bool FUSE = (NWN == 6), bool OSTG = false>
 hipError_t launch_cost_t(hipStream_t st, const void *Lt, const void *WA, int Mp, int Kb, int Pp,
                          int p0, int np, const uint64_t *mask, uint64_t *partial,
                          uint64_t *pbound, int node_base, const Dyn *dyn, int batch,
@@ -941,7 +1026,15 @@ hipError_t launch_cost_t(hipStream_t st, const void *Lt, const void *WA, int Mp,
                          uint32_t *cache = nullptr) {
     constexpr int BNK = NWN * 64;
     constexpr bool WIDE = BNK > BN;
-    const void *fn = reinterpret_cast<const void *>(&k_cost_topk<DT, RMAP, NWN, FUSE>);
+    // the wide int8 tile with overflow lists: staged through LDS when every
+    // tile's entries fit the scratch (Ovf::tile_max), else the global loop
+    if constexpr (WIDE && DT == NAS_DT_I8 && !OSTG) {
+        if (ov.ptr && !ov.row_pod && !ov.row_count && ov.tile_max <= OVF_STAGE_ENTRIES)
+            return launch_cost_t<DT, RMAP, NWN, FUSE, true>(st, Lt, WA, Mp, Kb, Pp, p0, np, mask,
+                                                            partial, pbound, node_base, dyn, batch,
+                                                            ov, rowmap, fs, cache);
+    }
+    const void *fn = reinterpret_cast<const void *>(&k_cost_topk<DT, RMAP, NWN, FUSE, OSTG>);
     constexpr int lds = 2 * (BM + BNK) * BKB;
     static std::atomic<unsigned long long> attr_set{0};
     hipError_t e = set_lds_once(fn, lds, attr_set);
@@ -964,7 +1057,7 @@ hipError_t launch_cost_t(hipStream_t st, const void *Lt, const void *WA, int Mp,
     const int *dhp = dyn ? dyn->hi_ptr : nullptr;
     // the wide tile's launch end rides in dyn_hi (unused without a window)
     const int dhi = WIDE ? p0 + np : dh;
-    k_cost_topk<DT, RMAP, NWN, FUSE><<<dim3(n_mt * n_nt, batch), 128 * NWN, lds, st>>>(
+    k_cost_topk<DT, RMAP, NWN, FUSE, OSTG><<<dim3(n_mt * n_nt, batch), 128 * NWN, lds, st>>>(
         lt, wa, Kb, n_mt, n_nt, p0, Pp, mk, pa, pb, node_base, ds, dhi, dhp, ov, rowmap, fs,
         reinterpret_cast<unsigned *>(cache));
     return hipGetLastError();
@@ -973,6 +1066,14 @@ hipError_t launch_cost_t(hipStream_t st, const void *Lt, const void *WA, int Mp,
 }  // namespace
 
 int cost_tile_pods(int) { return WIDE_PODS; }
+
+// wide tiles start at a launch's p0 (a multiple of BN) + 384 nt: multiples of 128
+int32_t ovf_window_max(const int32_t *ptr, int64_t rows) {
+    int32_t mx = 0;
+    for (int64_t s = 0; s < rows; s += 128)
+        mx = std::max(mx, ptr[std::min<int64_t>(s + WIDE_PODS, rows)] - ptr[s]);
+    return mx;
+}
 
 // Kp: padded contraction length in ELEMENTS; np: pods, multiple of BN,
 // p0 + np <= Pp; Mp multiple of BM.
@@ -984,7 +1085,14 @@ hipError_t launch_cost_topk(hipStream_t st, int dtype, const void *Lt, const voi
     if (fit && (dyn || rowmap)) return hipErrorInvalidValue;  // windows keep the k_fit mask
     if (cache && (dyn || rowmap)) return hipErrorInvalidValue;  // the cache: main pod ranges
     if (!fit && wide && !dyn && !rowmap) return hipErrorInvalidValue;  // the wide tile fuses
+#ifdef NAS_DIAG_NO_OVF
+    // DIAGNOSTIC ONLY (a variant build, make OUT=.. BUILD=.. EXTRA=-DNAS_DIAG_NO_OVF,
+    // never the product): no launch seeds its overflow entries -- costs of
+    // pods with entries are WRONG; it times the kernel without the seeding
+    const Ovf ov = Ovf{};
+#else
     const Ovf ov = ovf ? *ovf : Ovf{};
+#endif
     if (rowmap && (!dyn || batch != 1)) return hipErrorInvalidValue;
 #define NAS_COST_DISPATCH(DTV, KB, OVV)                                                            \
     (rowmap ? launch_cost_t<DTV, true>(st, Lt, WA, Mp, KB, Pp, p0, np, mask, partial, pbound,     \

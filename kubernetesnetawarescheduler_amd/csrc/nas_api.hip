@@ -261,6 +261,7 @@ int upload_ovf(nas_ctx *ctx, const std::vector<int32_t> &ptr, const std::vector<
                const std::vector<int32_t> &e) {
     ctx->ovf_n = (int64_t)m.size();
     if (m.empty()) return NAS_OK;
+    ctx->ovf_tile_max = nas::ovf_window_max(ptr.data(), (int64_t)ptr.size() - 1);
     OK(nas::ensure(ctx, ctx->ovf_ptr, ptr.size() * 4));
     OK(nas::ensure(ctx, ctx->ovf_m, m.size() * 4));
     OK(nas::ensure(ctx, ctx->ovf_e, e.size() * 4));
@@ -301,6 +302,7 @@ nas::Ovf make_ovf(const nas_ctx *ctx, const int32_t *row_pod = nullptr,
     o.row_pod = row_pod;
     o.row_count = row_count;
     o.N = ctx->N;
+    o.tile_max = ctx->ovf_tile_max;
     return o;
 }
 
@@ -3657,6 +3659,7 @@ static int synth(nas_ctx *ctx, uint64_t seed, int32_t B, int32_t n_nodes, int32_
                                                  ctx->ovf_m.as<int32_t>(), ctx->ovf_e.as<int32_t>()));
             HIPCK(hipStreamSynchronize(ctx->stream));
             ctx->ovf_n = tot;
+            ctx->ovf_tile_max = nas::ovf_window_max(ptr.data(), (int64_t)rows);
         }
         ctx->L_abs_max = 127;  // bound of the synthetic latency (<= 104; profile 1 <= 127), every rank
         ctx->B = B;

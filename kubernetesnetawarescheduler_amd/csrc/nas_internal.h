@@ -28,6 +28,13 @@ constexpr int COST_BN = 256;
 // launch's end (k = 2 mod 3), whose results it discards
 constexpr int WA_PAD_ROWS = 256;
 constexpr int COST_BKB = 128;  // bytes of K per stage (128 int8 or 64 bf16)
+// overflow entries (nas::Ovf) of one wide tile that its prologue stages through
+// LDS: per entry a 256-byte latency-row segment and an (m, e) record in the
+// second staging image (80 KiB, idle until the K loop's first iteration), as
+// many as fit in whole 1 KiB LDS-DMA pieces of four segments: 81920 / 264 =
+// 310 -> 308.  Traffic with a fuller tile seeds from global memory as before
+// (launch_cost_topk picks the kernel by Ovf::tile_max)
+constexpr int OVF_STAGE_ENTRIES = 308;
 
 inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
@@ -88,7 +95,12 @@ struct Ovf {
     const int32_t *row_pod = nullptr;
     const int32_t *row_count = nullptr;
     int N = 0;  // rows of one cluster's Lr
+    // most entries of any 384 consecutive rows from a multiple of 128 (where
+    // wide tiles start): ovf_window_max over ptr
+    int tile_max = 0x7fffffff;
 };
+// (host) that maximum for ptr[0 .. rows]
+int32_t ovf_window_max(const int32_t *ptr, int64_t rows);
 
 // In-process transport (nas_comm_init_local): G contexts of one process, each
 // driven by its own host thread, exchange candidate lists through device
@@ -184,6 +196,7 @@ struct nas_ctx {
     // exact int32 traffic (nas::Ovf): entries outside the int8 plane, and Lr
     nas::DevBuf ovf_ptr, ovf_m, ovf_e, Lr;
     int64_t ovf_n = 0;          // entries (0: the plane is the traffic)
+    int32_t ovf_tile_max = 0;   // nas::ovf_window_max of ovf_ptr (Ovf::tile_max)
     bool lr_valid = false;      // Lr matches the uploaded latency
     int64_t wa_abs_row_max = 0; // max over pods of sum_m |WA[p,m]| (int8 path)
     int32_t L_abs_max = 0;      // max |L| (int8 path)
