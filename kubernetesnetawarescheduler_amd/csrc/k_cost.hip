@@ -32,6 +32,7 @@
 // exactness bound (klist.h) -> merged across the two node-half waves through
 // LDS -> partial[node_tile][pod][8] + pbound[node_tile][pod] (72 B per pod
 // per tile).
+#include "fit_wave.h"
 #include "klist.h"
 
 #include <type_traits>
@@ -321,13 +322,11 @@ k_cost_topk(const unsigned char *__restrict__ Lt, const unsigned char *__restric
     // with no k_fit between them -- a fit launch in front of every cost
     // launch could not start until a wide workgroup drained its CU, and the
     // cost launch behind it then waited too).  The workgroup decides the fit
-    // words itself, exactly as k_fit does, after its main loop: per 64-node
-    // chunk the minima / maxima of the free capacity (read then -- after the
-    // previous chunks' commits and possibly during this chunk's predecessor's;
-    // capacity only shrinks, so a "does not fit" read at any earlier time
-    // still holds at the pod's turn) decide every pod that fits all valid
-    // nodes or none; the rest compare against the lanes' capacities (three
-    // ballots).  The words land where the k_fit mask words would (mwp).
+    // words itself, by k_fit's rule (fit_wave.h), after its main loop, from
+    // the free capacity read then -- after the previous chunks' commits and
+    // possibly during this chunk's predecessor's; capacity only shrinks, so a
+    // "does not fit" read at any earlier time still holds at the pod's turn.
+    // The words land where the k_fit mask words would (mwp).
     int rq[FUSE ? AN : 1][3];
     int fcap[2][3];
     auto fit_issue = [&]() {  // the requests of the lane's pods, its nodes' capacities
@@ -358,41 +357,27 @@ k_cost_topk(const unsigned char *__restrict__ Lt, const unsigned char *__restric
     auto fit_words = [&]() {
 #pragma unroll
         for (int mi2 = 0; mi2 < 2; ++mi2) {
+            // the chunk state filled here, not by FitChunk's load / reduce:
+            // with those the bf16 tiles took 2-6 more registers and spilled
             const bool real = mt * BM + wm * 128 + mi2 * 64 + lane < fs.nloc;
-            const u64 valid = __builtin_amdgcn_ballot_w64(real);
-            int mn[3], mx[3];
+            FitChunk<false> ch;
+            ch.valid = __builtin_amdgcn_ballot_w64(real);
 #pragma unroll
             for (int r = 0; r < 3; ++r) {
-                int a = real ? fcap[mi2][r] : 0x7fffffff, x = real ? fcap[mi2][r] : (int)0x80000000;
+                ch.f[r] = fcap[mi2][r];
+                int a = real ? ch.f[r] : 0x7fffffff, x = real ? ch.f[r] : (int)0x80000000;
 #pragma unroll
                 for (int o = 32; o; o >>= 1) {
                     a = min(a, __shfl_xor(a, o));
                     x = max(x, __shfl_xor(x, o));
                 }
-                mn[r] = __builtin_amdgcn_readfirstlane(a);
-                mx[r] = __builtin_amdgcn_readfirstlane(x);
+                ch.mn[r] = __builtin_amdgcn_readfirstlane(a);
+                ch.mx[r] = __builtin_amdgcn_readfirstlane(x);
             }
+            // lanes l and l + PB (+ 2 PB, 3 PB) hold the same pod
 #pragma unroll
-            for (int ni = 0; ni < AN; ++ni) {
-                const int a = rq[ni][0], bq = rq[ni][1], d = rq[ni][2];
-                const bool all = a <= mn[0] && bq <= mn[1] && d <= mn[2];
-                const bool none = a > mx[0] || bq > mx[1] || d > mx[2];
-                u64 word = all ? valid : 0ull;
-                // lanes l and l + PB (+ 2 PB, 3 PB) hold the same pod: decide
-                // lanes 0..PB-1
-                u64 rest = __builtin_amdgcn_ballot_w64(!all && !none) & ((1ull << PB) - 1);
-                while (rest) {
-                    const int i = (int)__builtin_ctzll(rest);
-                    rest &= rest - 1;
-                    const int ra = __builtin_amdgcn_readlane(a, i), rb = __builtin_amdgcn_readlane(bq, i);
-                    const int rd = __builtin_amdgcn_readlane(d, i);
-                    const u64 m = __builtin_amdgcn_ballot_w64(ra <= fcap[mi2][0]) &
-                                  __builtin_amdgcn_ballot_w64(rb <= fcap[mi2][1]) &
-                                  __builtin_amdgcn_ballot_w64(rd <= fcap[mi2][2]);
-                    if ((lane & (PB - 1)) == i) word = m;
-                }
-                *fit_slot(ni, mi2) = word;
-            }
+            for (int ni = 0; ni < AN; ++ni)
+                *fit_slot(ni, mi2) = fit_decide<PB>(ch, lane, rq[ni][0], rq[ni][1], rq[ni][2], true);
         }
     };
 

@@ -6,62 +6,27 @@
 // req[r][p] <= free[r][n] for r in {cpu millicores, memory KiB, pod slots}.
 //
 // Layout: lane-per-NODE.  Each wave owns one 64-node chunk c (lane j = node
-// 64c + j, its three free capacities in VGPRs, read once, plus the chunk's
-// minima and maxima, wave-uniform) and walks its pods 64 at a time, lane i
-// holding pod i's requests:
-//   * three v_cmp against the chunk minima decide, for all 64 pods at once,
-//     the pods that fit EVERY valid node of the chunk (word = valid-node
-//     mask), three against the maxima the pods that fit NONE (word = 0);
-//   * each remaining pod is broadcast (v_readlane) and compared against the
-//     64 lanes' capacities: three ballots ANDed are its word, written
-//     into its lane;
-// and the 64 words leave in one coalesced 8-byte-per-lane store:
+// 64c + j) and walks its pods 64 at a time, lane i holding pod i's requests;
+// the decision itself -- the chunk's minima and maxima first, the remaining
+// pods broadcast one by one -- is fit_wave.h's (FitChunk, fit_decide), shared
+// with the cost kernel's fused fit.  The 64 words leave in one coalesced
+// 8-byte-per-lane store:
 //   mask[c * Pp + p]  bit j  <=>  pod p fits local node 64c + j.
 // Requests are small against node capacity until nodes fill up, so most
 // (pod, chunk) pairs cost 1/64 of a compare; the kernel runs near the rate of
 // its mask write (P*N/8 bytes, HBM) -- see DESIGN.md.
 //
-// Constrained form (C = true, nas::Elig: node selectors and taints): the lane
-// also keeps its node's label and taint words in VGPRs, the wave the chunk's
-// AND / OR of each (wave-uniform, padding lanes excluded), and a pod's
-// require / tolerate words travel with its requests.  eligible(p, n) <=>
-// (labels[n] & require[p]) == require[p] and (taints[n] & ~tolerate[p]) == 0:
-//   * "fits every valid node" also needs require & ~AND(labels) == 0 and
-//     OR(taints) & ~tolerate == 0;
-//   * "fits none" also holds when require & ~OR(labels) != 0 or
-//     AND(taints) & ~tolerate != 0;
-//   * the remaining pods take two more ballots each.
-// The unconstrained kernels are the C = false instantiations of the same
-// bodies (every constrained statement sits under `if constexpr (C)`).
-#include "nas_internal.h"
+// Constrained form (C = true, nas::Elig: node selectors and taints): a pod's
+// require / tolerate words travel with its requests.  The unconstrained
+// kernels are the C = false instantiations of the same bodies.
+#include "fit_wave.h"
 
 namespace nas {
 namespace {
 
 constexpr int FIT_THREADS = 256;  // 4 waves = 4 node chunks per block
 constexpr int FIT_WAVES = FIT_THREADS / 64;
-constexpr int FIT_GROUPS_MAX = 8;  // 64-pod groups per block (at most 512 pods)
-constexpr int FIT_PF = 2;          // groups of requests in flight ahead of the one decided
-typedef unsigned long long u64;
-
-// the chunk's AND / OR of a per-node word over its valid lanes, wave-uniform
-__device__ __forceinline__ u64 wave_and(u64 v) {
-#pragma unroll
-    for (int o = 32; o; o >>= 1) v &= __shfl_xor(v, o);
-    return ((u64)(unsigned)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) |
-           (unsigned)__builtin_amdgcn_readfirstlane((int)v);
-}
-__device__ __forceinline__ u64 wave_or(u64 v) {
-#pragma unroll
-    for (int o = 32; o; o >>= 1) v |= __shfl_xor(v, o);
-    return ((u64)(unsigned)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) |
-           (unsigned)__builtin_amdgcn_readfirstlane((int)v);
-}
-// lane i's 64-bit word, wave-uniform
-__device__ __forceinline__ u64 readlane64(u64 v, int i) {
-    return ((u64)(unsigned)__builtin_amdgcn_readlane((int)(v >> 32), i) << 32) |
-           (unsigned)__builtin_amdgcn_readlane((int)v, i);
-}
+constexpr int FIT_PF = 2;  // groups of requests in flight ahead of the one decided
 
 // G = 64-pod groups per wave (compile time: the group loop is unrolled and the
 // request ring stays in registers).  Measured at the C3 shape (10k nodes x 100k
@@ -112,51 +77,10 @@ fit_body(const int *cap, int N, int n0, int nloc, int n_chunks,
             rt[g] = el.tolerate[q];
         }
     }
-    // relaxed atomic loads: nas_place filters against the working capacity
-    // while the commit stream publishes into it; padding nodes never fit
-    int fc = -1, fm = -1, fp = -1;
-    if (nl < nloc) {
-        int *cp = const_cast<int *>(cap) + n0 + nl;
-        fc = __hip_atomic_load(cp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        fm = __hip_atomic_load(cp + N, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        fp = __hip_atomic_load(cp + 2 * (size_t)N, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    // the chunk's valid nodes, its smallest and largest capacities (padding
-    // lanes excluded: they fit nothing), wave-uniform (SGPRs)
-    const bool real = nl < nloc;
-    const unsigned long long valid = __builtin_amdgcn_ballot_w64(real);
-    int mc = real ? fc : 0x7fffffff, mm = real ? fm : 0x7fffffff, mp = real ? fp : 0x7fffffff;
-    int xc = real ? fc : (int)0x80000000, xm = real ? fm : (int)0x80000000;
-    int xp = real ? fp : (int)0x80000000;
-#pragma unroll
-    for (int o = 32; o; o >>= 1) {
-        mc = min(mc, __shfl_xor(mc, o));
-        mm = min(mm, __shfl_xor(mm, o));
-        mp = min(mp, __shfl_xor(mp, o));
-        xc = max(xc, __shfl_xor(xc, o));
-        xm = max(xm, __shfl_xor(xm, o));
-        xp = max(xp, __shfl_xor(xp, o));
-    }
-    mc = __builtin_amdgcn_readfirstlane(mc);
-    mm = __builtin_amdgcn_readfirstlane(mm);
-    mp = __builtin_amdgcn_readfirstlane(mp);
-    xc = __builtin_amdgcn_readfirstlane(xc);
-    xm = __builtin_amdgcn_readfirstlane(xm);
-    xp = __builtin_amdgcn_readfirstlane(xp);
-    // (constrained) the node's label / taint words and the chunk's AND / OR of
-    // each over its valid nodes
-    u64 lb = 0, tn = 0, l_and = 0, l_or = 0, t_and = 0, t_or = 0;
-    if constexpr (C) {
-        if (real) {
-            lb = el.labels[n0 + nl];
-            tn = el.taints[n0 + nl];
-        }
-        l_and = wave_and(real ? lb : ~0ull);
-        l_or = wave_or(lb);
-        t_and = wave_and(real ? tn : ~0ull);
-        t_or = wave_or(tn);
-    }
-    const unsigned vlo = (unsigned)valid, vhi = (unsigned)(valid >> 32);
+    FitChunk<C> ch;
+    ch.load(cap, N, n0 + nl, nl < nloc);
+    ch.reduce(nl < nloc);
+    if constexpr (C) ch.constrain(el, n0 + nl, nl < nloc);
 #pragma unroll
     for (int g = 0; g < G; ++g) {
         const int pb = pb0 + 64 * g;
@@ -175,43 +99,8 @@ fit_body(const int *cap, int N, int n0, int nloc, int n_chunks,
             }
         }
         const bool in = pb + lane < pend;
-        // 64 pods at once against the chunk's extremes: fits every valid node
-        // (requests <= the minima) or none (some request > its maximum)
-        unsigned long long all, none;
-        if constexpr (C) {
-            all = __builtin_amdgcn_ballot_w64(in && a0 <= mc && b0 <= mm && d0 <= mp &&
-                                              (q0 & ~l_and) == 0 && (t_or & ~t0) == 0);
-            none = __builtin_amdgcn_ballot_w64(in && (a0 > xc || b0 > xm || d0 > xp ||
-                                                      (q0 & ~l_or) != 0 || (t_and & ~t0) != 0));
-        } else {
-            all = __builtin_amdgcn_ballot_w64(in && a0 <= mc && b0 <= mm && d0 <= mp);
-            none = __builtin_amdgcn_ballot_w64(in && (a0 > xc || b0 > xm || d0 > xp));
-        }
-        unsigned long long rest = __builtin_amdgcn_ballot_w64(in) & ~all & ~none;
-        unsigned lo = ((all >> lane) & 1) ? vlo : 0u, hi = ((all >> lane) & 1) ? vhi : 0u;
-        // the others one by one: the pod's (broadcast) requests against the
-        // lanes' capacities, three ballots ANDed, written into its lane
-        while (rest) {
-            const int i = (int)__builtin_ctzll(rest);
-            rest &= rest - 1;
-            const int a = __builtin_amdgcn_readlane(a0, i), b = __builtin_amdgcn_readlane(b0, i);
-            const int d = __builtin_amdgcn_readlane(d0, i);
-            unsigned long long m = __builtin_amdgcn_ballot_w64(a <= fc) &
-                                   __builtin_amdgcn_ballot_w64(b <= fm) &
-                                   __builtin_amdgcn_ballot_w64(d <= fp);
-            if constexpr (C) {
-                const u64 qi = readlane64(q0, i), ti = readlane64(t0, i);
-                m &= __builtin_amdgcn_ballot_w64((lb & qi) == qi) &
-                     __builtin_amdgcn_ballot_w64((tn & ~ti) == 0);
-            }
-            if (lane == i) {
-                lo = (unsigned)m;
-                hi = (unsigned)(m >> 32);
-            }
-        }
-        if (in)
-            __builtin_nontemporal_store(((unsigned long long)hi << 32) | lo,
-                                        mask + (size_t)c * Pp + pb + lane);
+        const u64 word = fit_decide<64>(ch, lane, a0, b0, d0, in, q0, t0);
+        if (in) __builtin_nontemporal_store(word, mask + (size_t)c * Pp + pb + lane);
     }
 }
 
@@ -266,44 +155,6 @@ fit2_body(const int *cap, int N, int n0, int nloc, int n_chunks,
     if (c >= n_chunks) return;
     const int nl = c * 64 + lane;
     const int pend = min(p_end, pb0 + 128 * G);
-    int fc = -1, fm = -1, fp = -1;
-    if (nl < nloc) {
-        int *cp = const_cast<int *>(cap) + n0 + nl;
-        fc = __hip_atomic_load(cp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        fm = __hip_atomic_load(cp + N, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        fp = __hip_atomic_load(cp + 2 * (size_t)N, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    const bool real = nl < nloc;
-    const unsigned long long valid = __builtin_amdgcn_ballot_w64(real);
-    int mc = real ? fc : 0x7fffffff, mm = real ? fm : 0x7fffffff, mp = real ? fp : 0x7fffffff;
-    int xc = real ? fc : (int)0x80000000, xm = real ? fm : (int)0x80000000;
-    int xp = real ? fp : (int)0x80000000;
-#pragma unroll
-    for (int o = 32; o; o >>= 1) {
-        mc = min(mc, __shfl_xor(mc, o));
-        mm = min(mm, __shfl_xor(mm, o));
-        mp = min(mp, __shfl_xor(mp, o));
-        xc = max(xc, __shfl_xor(xc, o));
-        xm = max(xm, __shfl_xor(xm, o));
-        xp = max(xp, __shfl_xor(xp, o));
-    }
-    mc = __builtin_amdgcn_readfirstlane(mc);
-    mm = __builtin_amdgcn_readfirstlane(mm);
-    mp = __builtin_amdgcn_readfirstlane(mp);
-    xc = __builtin_amdgcn_readfirstlane(xc);
-    xm = __builtin_amdgcn_readfirstlane(xm);
-    xp = __builtin_amdgcn_readfirstlane(xp);
-    u64 lb = 0, tn = 0, l_and = 0, l_or = 0, t_and = 0, t_or = 0;  // (constrained, as in fit_body)
-    if constexpr (C) {
-        if (real) {
-            lb = el.labels[n0 + nl];
-            tn = el.taints[n0 + nl];
-        }
-        l_and = wave_and(real ? lb : ~0ull);
-        l_or = wave_or(lb);
-        t_and = wave_and(real ? tn : ~0ull);
-        t_or = wave_or(tn);
-    }
     typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
     // requests of the lane's two pods (8-byte loads; rows past the range read
     // the last even pair, loaded, never stored); constrained: their require /
@@ -320,7 +171,11 @@ fit2_body(const int *cap, int N, int n0, int nloc, int n_chunks,
         }
     };
     int2 ra, rb, rd;
-    load2(pb0, ra, rb, rd);
+    load2(pb0, ra, rb, rd);  // (ahead of the chunk, as in fit_body: behind it, one VGPR more at G = 1)
+    FitChunk<C> ch;
+    ch.load(cap, N, n0 + nl, nl < nloc);
+    ch.reduce(nl < nloc);
+    if constexpr (C) ch.constrain(el, n0 + nl, nl < nloc);
 #pragma unroll
     for (int g = 0; g < G; ++g) {
         const int pb = pb0 + 128 * g;
@@ -329,43 +184,8 @@ fit2_body(const int *cap, int N, int n0, int nloc, int n_chunks,
         const u64x2 q0 = rq, t0 = rt;
         if (g + 1 < G) load2(pb + 128, ra, rb, rd);  // next group in flight
         const bool in0 = pb + 2 * lane < pend, in1 = pb + 2 * lane + 1 < pend;
-        unsigned long long w0 = 0, w1 = 0;
-        // half h: the lanes' pod pb + 2 * lane + h
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int a = h ? a0.y : a0.x, b = h ? b0.y : b0.x, d = h ? d0.y : d0.x;
-            const bool in = h ? in1 : in0;
-            const u64 pq = h ? q0.y : q0.x, pt = h ? t0.y : t0.x;
-            unsigned long long all, none;
-            if constexpr (C) {
-                all = __builtin_amdgcn_ballot_w64(in && a <= mc && b <= mm && d <= mp &&
-                                                  (pq & ~l_and) == 0 && (t_or & ~pt) == 0);
-                none = __builtin_amdgcn_ballot_w64(in && (a > xc || b > xm || d > xp ||
-                                                          (pq & ~l_or) != 0 || (t_and & ~pt) != 0));
-            } else {
-                all = __builtin_amdgcn_ballot_w64(in && a <= mc && b <= mm && d <= mp);
-                none = __builtin_amdgcn_ballot_w64(in && (a > xc || b > xm || d > xp));
-            }
-            unsigned long long rest = __builtin_amdgcn_ballot_w64(in) & ~all & ~none;
-            unsigned long long word = ((all >> lane) & 1) ? valid : 0ull;
-            while (rest) {
-                const int i = (int)__builtin_ctzll(rest);
-                rest &= rest - 1;
-                const int ba = __builtin_amdgcn_readlane(a, i), bb = __builtin_amdgcn_readlane(b, i);
-                const int bd = __builtin_amdgcn_readlane(d, i);
-                unsigned long long m = __builtin_amdgcn_ballot_w64(ba <= fc) &
-                                       __builtin_amdgcn_ballot_w64(bb <= fm) &
-                                       __builtin_amdgcn_ballot_w64(bd <= fp);
-                if constexpr (C) {
-                    const u64 qi = readlane64(pq, i), ti = readlane64(pt, i);
-                    m &= __builtin_amdgcn_ballot_w64((lb & qi) == qi) &
-                         __builtin_amdgcn_ballot_w64((tn & ~ti) == 0);
-                }
-                if (lane == i) word = m;
-            }
-            if (h) w1 = word;
-            else w0 = word;
-        }
+        const u64 w0 = fit_decide<64>(ch, lane, a0.x, b0.x, d0.x, in0, q0.x, t0.x);
+        const u64 w1 = fit_decide<64>(ch, lane, a0.y, b0.y, d0.y, in1, q0.y, t0.y);
         unsigned long long *dst = mask + (size_t)c * Pp + pb + 2 * lane;
         // plain stores: 24.7-24.9 vs 25.1-25.8 us for non-temporal ones at the
         // C3 shape (profiles/r04_ab_fold.txt, fitpl)
@@ -410,54 +230,43 @@ hipError_t launch_fit(hipStream_t st, const int32_t *cap, int N, int n0, int nlo
         return hipErrorInvalidValue;
     if (np <= 0) return hipSuccess;
     const int n_chunks = Mp / 64;
-    if (!rowmap && p0 % 2 == 0) {  // two pods per lane (k_fit2)
-        // pods per block: up to 512 (4 groups of 128), fewer on small launches
-        const int yb2 = (n_chunks + FIT_WAVES - 1) / FIT_WAVES;
-        const long long groups2 = ((long long)np + 127) / 128 * yb2;
-        const int k2 = (int)std::max(1LL, std::min<long long>(4, groups2 / 2048));
-        const int G2 = k2 >= 4 ? 4 : k2 >= 2 ? 2 : 1;
-        dim3 grid2((np + 128 * G2 - 1) / (128 * G2) + (dyn ? 1 : 0), yb2, batch);
-        auto *m2 = reinterpret_cast<unsigned long long *>(mask);
-        const int pe2 = dyn ? dyn->hi : p0 + np;
-        const int *ds2 = dyn ? dyn->start : nullptr, *dh2 = dyn ? dyn->hi_ptr : nullptr;
-        const int dw2 = dyn ? dyn->win : 0;
-#define NAS_FIT2(GV)                                                                                 \
-    if (el)                                                                                          \
-        k_fit2_c<GV><<<grid2, FIT_THREADS, 0, st>>>(cap, N, n0, nloc, n_chunks, req, Pp, p0, pe2, m2, \
-                                                    ds2, dw2, dh2, *el);                             \
-    else                                                                                             \
-        k_fit2<GV><<<grid2, FIT_THREADS, 0, st>>>(cap, N, n0, nloc, n_chunks, req, Pp, p0, pe2, m2, ds2, dw2, dh2)
-        switch (G2) {
-        case 4: NAS_FIT2(4); break;
-        case 2: NAS_FIT2(2); break;
-        default: NAS_FIT2(1); break;
-        }
-#undef NAS_FIT2
-        return hipGetLastError();
-    }
+    // one pod per lane (k_fit, groups of 64 pods), or two (k_fit2, groups of
+    // 128) over a main range from an even pod
+    const bool pair = !rowmap && p0 % 2 == 0;
+    const int gp = pair ? 128 : 64;
     // pods per block: up to 512, fewer when the launch is small, so a rescore
     // slot's few thousand pods still spread over ~2k blocks (each wave's pod
     // groups run back to back: latency, not work, sets a small launch's time)
     const int yb = (n_chunks + FIT_WAVES - 1) / FIT_WAVES;
-    const long long groups = ((long long)np + 63) / 64 * yb;
-    const int k = (int)std::max(1LL, std::min<long long>(FIT_GROUPS_MAX, groups / 2048));
+    const long long groups = ((long long)np + gp - 1) / gp * yb;
+    const int k = (int)std::max(1LL, std::min<long long>(512 / gp, groups / 2048));
     const int G = k >= 8 ? 8 : k >= 4 ? 4 : k >= 2 ? 2 : 1;  // instantiated group counts
-    dim3 grid((np + 64 * G - 1) / (64 * G), yb, batch);
+    // (pairs: a window from an odd pod starts one pod early, so one more block)
+    dim3 grid((np + gp * G - 1) / (gp * G) + (pair && dyn ? 1 : 0), yb, batch);
     auto *m = reinterpret_cast<unsigned long long *>(mask);
     const int pe = dyn ? dyn->hi : p0 + np;
     const int *ds = dyn ? dyn->start : nullptr, *dh = dyn ? dyn->hi_ptr : nullptr;
     const int dw = dyn ? dyn->win : 0, rs = rowmap ? req_stride : Pp;
-#define NAS_FIT(GV)                                                                                  \
-    if (el)                                                                                          \
-        k_fit_c<GV><<<grid, FIT_THREADS, 0, st>>>(cap, N, n0, nloc, n_chunks, req, Pp, p0, pe, m, ds, \
-                                                  dw, dh, rowmap, rs, *el);                          \
-    else                                                                                             \
-        k_fit<GV><<<grid, FIT_THREADS, 0, st>>>(cap, N, n0, nloc, n_chunks, req, Pp, p0, pe, m, ds, dw, dh, rowmap, rs)
-    switch (G) {
-    case 8: NAS_FIT(8); break;
-    case 4: NAS_FIT(4); break;
-    case 2: NAS_FIT(2); break;
-    default: NAS_FIT(1); break;
+#define NAS_FIT(K, GV, ...)                                                                         \
+    if (el)                                                                                         \
+        K##_c<GV><<<grid, FIT_THREADS, 0, st>>>(cap, N, n0, nloc, n_chunks, req, Pp, p0, pe, m, ds, \
+                                                dw, dh, ##__VA_ARGS__, *el);                        \
+    else                                                                                            \
+        K<GV><<<grid, FIT_THREADS, 0, st>>>(cap, N, n0, nloc, n_chunks, req, Pp, p0, pe, m, ds, dw, \
+                                            dh, ##__VA_ARGS__)
+    if (pair) {
+        switch (G) {
+        case 4: NAS_FIT(k_fit2, 4); break;
+        case 2: NAS_FIT(k_fit2, 2); break;
+        default: NAS_FIT(k_fit2, 1); break;
+        }
+    } else {
+        switch (G) {
+        case 8: NAS_FIT(k_fit, 8, rowmap, rs); break;
+        case 4: NAS_FIT(k_fit, 4, rowmap, rs); break;
+        case 2: NAS_FIT(k_fit, 2, rowmap, rs); break;
+        default: NAS_FIT(k_fit, 1, rowmap, rs); break;
+        }
     }
 #undef NAS_FIT
     return hipGetLastError();

@@ -45,31 +45,9 @@ k_fit2(const int *cap, int N, int n0, int nloc, int n_chunks, const int *__restr
         rb[g] = req[Pp + q];
         rd[g] = req[2 * (size_t)Pp + q];
     }
-    int fc = -1, fm = -1, fp = -1;
-    if (nl < nloc) {
-        int *cp = const_cast<int *>(cap) + n0 + nl;
-        fc = __hip_atomic_load(cp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        fm = __hip_atomic_load(cp + N, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        fp = __hip_atomic_load(cp + 2 * (size_t)N, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    const bool real = nl < nloc;
-    const unsigned long long valid = __builtin_amdgcn_ballot_w64(real);
-    int mc = real ? fc : 0x7fffffff, mm = real ? fm : 0x7fffffff, mp = real ? fp : 0x7fffffff;
-    int xc = real ? fc : (int)0x80000000, xm = real ? fm : (int)0x80000000;
-    int xp = real ? fp : (int)0x80000000;
-#pragma unroll
-    for (int o = 32; o; o >>= 1) {
-        mc = min(mc, __shfl_xor(mc, o));
-        mm = min(mm, __shfl_xor(mm, o));
-        mp = min(mp, __shfl_xor(mp, o));
-        xc = max(xc, __shfl_xor(xc, o));
-        xm = max(xm, __shfl_xor(xm, o));
-        xp = max(xp, __shfl_xor(xp, o));
-    }
-    mc = __builtin_amdgcn_readfirstlane(mc); mm = __builtin_amdgcn_readfirstlane(mm);
-    mp = __builtin_amdgcn_readfirstlane(mp); xc = __builtin_amdgcn_readfirstlane(xc);
-    xm = __builtin_amdgcn_readfirstlane(xm); xp = __builtin_amdgcn_readfirstlane(xp);
-    const unsigned vlo = (unsigned)valid, vhi = (unsigned)(valid >> 32);
+    FitChunk<false> ch;
+    ch.load(cap, N, n0 + nl, nl < nloc);
+    ch.reduce(nl < nloc);
 #pragma unroll
     for (int g = 0; g < G; ++g) {
         const int pb = pb0 + 64 * g;
@@ -83,25 +61,8 @@ k_fit2(const int *cap, int N, int n0, int nloc, int n_chunks, const int *__restr
             rd[s] = req[2 * (size_t)Pp + q];
         }
         const bool in = pb + lane < pend;
-        const unsigned long long all = __builtin_amdgcn_ballot_w64(in && a0 <= mc && b0 <= mm && d0 <= mp);
-        const unsigned long long none = __builtin_amdgcn_ballot_w64(in && (a0 > xc || b0 > xm || d0 > xp));
-        unsigned long long rest = __builtin_amdgcn_ballot_w64(in) & ~all & ~none;
-        unsigned lo = ((all >> lane) & 1) ? vlo : 0u, hi = ((all >> lane) & 1) ? vhi : 0u;
-        while (rest) {
-            const int i = (int)__builtin_ctzll(rest);
-            rest &= rest - 1;
-            const int a = __builtin_amdgcn_readlane(a0, i), b = __builtin_amdgcn_readlane(b0, i);
-            const int d = __builtin_amdgcn_readlane(d0, i);
-            const unsigned long long m = __builtin_amdgcn_ballot_w64(a <= fc) &
-                                         __builtin_amdgcn_ballot_w64(b <= fm) &
-                                         __builtin_amdgcn_ballot_w64(d <= fp);
-            if (lane == i) {
-                lo = (unsigned)m;
-                hi = (unsigned)(m >> 32);
-            }
-        }
+        const unsigned long long word = fit_decide<64>(ch, lane, a0, b0, d0, in);
         if (in) {
-            const unsigned long long word = ((unsigned long long)hi << 32) | lo;
             if constexpr (NT) __builtin_nontemporal_store(word, mask + (size_t)c * Pp + pb + lane);
             else mask[(size_t)c * Pp + pb + lane] = word;
         }
