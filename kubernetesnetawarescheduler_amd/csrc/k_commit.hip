@@ -757,19 +757,17 @@ k_commit_w(const u64 *__restrict__ cand_key, const u64 *__restrict__ cand_bound,
 
 bool commit_in_lds(int N) { return N <= LDS_CAP_MAX_NODES; }
 
-hipError_t launch_commit(hipStream_t st, const uint64_t *cand_key, const uint64_t *cand_bound,
-                         const int32_t *req, int Pp, int p_begin, int p_end, int32_t *cap, int N,
-                         int32_t *out_node, int32_t *out_cost, int32_t *halt, int batch,
-                         int32_t *pub, const uint8_t *zrow, int32_t *stage_node,
-                         int32_t *stage_cost, int32_t *stage_status) {
-    if (p_begin >= 0 && p_end <= p_begin) return hipSuccess;
-    // a batch stages whole clusters, [cluster][p_end] rows from pod 0
-    if (stage_node && (p_begin < 0 || (batch != 1 && p_begin != 0))) return hipErrorInvalidValue;
-    if (stage_status && batch != 1) return hipErrorInvalidValue;
-    auto *sc = reinterpret_cast<unsigned *>(stage_cost);
-    const auto *ck = reinterpret_cast<const u64 *>(cand_key);
-    const auto *cb = reinterpret_cast<const u64 *>(cand_bound);
-    auto *oc = reinterpret_cast<unsigned *>(out_cost);
+hipError_t launch_commit(hipStream_t st, const CommitArgs &a) {
+    if (const Pre pre = precheck(a); pre != Pre::Launch) return pre_error(pre);
+    const int32_t *req = a.req;
+    const int Pp = a.Pp, p_begin = a.p_begin, p_end = a.p_end, N = a.N, batch = a.batch;
+    int32_t *cap = a.cap, *out_node = a.out_node, *halt = a.halt, *pub = a.pub;
+    const uint8_t *zrow = a.zrow;
+    int32_t *stage_node = a.stage_node, *stage_status = a.stage_status;
+    auto *sc = reinterpret_cast<unsigned *>(a.stage_cost);
+    const auto *ck = reinterpret_cast<const u64 *>(a.cand_key);
+    const auto *cb = reinterpret_cast<const u64 *>(a.cand_bound);
+    auto *oc = reinterpret_cast<unsigned *>(a.out_cost_i);
     if (Pp <= ONE_WAVE_MAX_PODS && batch == 1) {
         if (N <= AOS_MAX_NODES) {
             const size_t lds = round_up(16 * (size_t)N, 256) + PF_BYTES;

@@ -946,6 +946,8 @@ constexpr int MERGE_LANES = 8;
 // wide tile admits nothing beside it either way: C3 within noise for 256 /
 // 512 / 1,024, profiles/r03_ab_merge_block.txt)
 constexpr int MERGE_BLOCK = 512;
+// dyn_flags: source / destination lists indexed from the window start (no caller sets them)
+constexpr int MERGE_SRC_WINDOW = 1, MERGE_DST_WINDOW = 2;
 
 __global__ void __launch_bounds__(MERGE_BLOCK)
 k_merge(const u64 *__restrict__ keys, const u64 *__restrict__ bounds, int n_lists,
@@ -1110,21 +1112,17 @@ hipError_t launch_cost_topk(hipStream_t st, int dtype, const void *Lt, const voi
 #undef NAS_COST_DISPATCH
 }
 
-hipError_t launch_merge(hipStream_t st, const uint64_t *keys, const uint64_t *bounds, int n_lists,
-                        int64_t stride, int64_t bstride, int src_p0, int p0, int np,
-                        uint64_t *cand_key, uint64_t *cand_bound, int dst_p0, const Dyn *dyn,
-                        int dyn_flags, int batch, int64_t dst_cluster_pods,
-                        const int32_t *dst_idx, int32_t *init_status) {
-    if (dyn) np = dyn->win;
-    if (np <= 0) return hipSuccess;
-    if (dst_idx && batch != 1) return hipErrorInvalidValue;
-    if (init_status && (dyn || batch != 1)) return hipErrorInvalidValue;
-    k_merge<<<dim3((int)(((int64_t)np * MERGE_LANES + MERGE_BLOCK - 1) / MERGE_BLOCK), batch),
+hipError_t launch_merge(hipStream_t st, const MergeArgs &a) {
+    if (const Pre pre = precheck(a); pre != Pre::Launch) return pre_error(pre);
+    const Dyn *dyn = a.dyn;
+    const int np = dyn ? dyn->win : a.np;
+    k_merge<<<dim3((int)(((int64_t)np * MERGE_LANES + MERGE_BLOCK - 1) / MERGE_BLOCK), a.batch),
               MERGE_BLOCK, 0, st>>>(
-        reinterpret_cast<const u64 *>(keys), reinterpret_cast<const u64 *>(bounds), n_lists, stride,
-        bstride, src_p0, p0, np, reinterpret_cast<u64 *>(cand_key),
-        reinterpret_cast<u64 *>(cand_bound), dst_p0, dyn ? dyn->start : nullptr, dyn ? dyn->hi : 0,
-        dyn_flags, (long long)dst_cluster_pods, dyn ? dyn->hi_ptr : nullptr, dst_idx, init_status);
+        reinterpret_cast<const u64 *>(a.keys), reinterpret_cast<const u64 *>(a.bounds), a.n_lists,
+        a.stride, a.bstride, a.src_p0, a.p0, np, reinterpret_cast<u64 *>(a.cand_key),
+        reinterpret_cast<u64 *>(a.cand_bound), a.dst_p0, dyn ? dyn->start : nullptr,
+        dyn ? dyn->hi : 0, /*dyn_flags=*/0, (long long)a.dst_cluster_pods,
+        dyn ? dyn->hi_ptr : nullptr, a.dst_idx, a.init_status);
     return hipGetLastError();
 }
 

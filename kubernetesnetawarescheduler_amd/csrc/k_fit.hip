@@ -218,18 +218,13 @@ k_fit2_c(const int *cap, int N, int n0, int nloc, int n_chunks,
 
 }  // namespace
 
-hipError_t launch_fit(hipStream_t st, const int32_t *cap, int N, int n0, int nloc, int Mp,
-                      const int32_t *req, int P, int Pp, int p0, int np, uint64_t *mask,
-                      const Dyn *dyn, int batch, const int32_t *rowmap, int req_stride,
-                      const Elig *el) {
-    (void)P;
-    if (rowmap && batch != 1) return hipErrorInvalidValue;
-    // the constraint words are one cluster's: [N] per node, [Pp] per pod of the
-    // main pod array (a row-mapped view reads them through its row map)
-    if (el && (batch != 1 || !el->labels || !el->taints || !el->require || !el->tolerate))
-        return hipErrorInvalidValue;
-    if (np <= 0) return hipSuccess;
-    const int n_chunks = Mp / 64;
+hipError_t launch_fit(hipStream_t st, const FitArgs &a) {
+    if (const Pre pre = precheck(a); pre != Pre::Launch) return pre_error(pre);
+    const int32_t *cap = a.cap, *req = a.req, *rowmap = a.rowmap;
+    const int N = a.N, n0 = a.n0, nloc = a.nloc, Pp = a.Pp, p0 = a.p0, np = a.np, batch = a.batch;
+    const Dyn *dyn = a.dyn;
+    const Elig *el = a.el;
+    const int n_chunks = a.Mp / 64;
     // one pod per lane (k_fit, groups of 64 pods), or two (k_fit2, groups of
     // 128) over a main range from an even pod
     const bool pair = !rowmap && p0 % 2 == 0;
@@ -243,10 +238,10 @@ hipError_t launch_fit(hipStream_t st, const int32_t *cap, int N, int n0, int nlo
     const int G = k >= 8 ? 8 : k >= 4 ? 4 : k >= 2 ? 2 : 1;  // instantiated group counts
     // (pairs: a window from an odd pod starts one pod early, so one more block)
     dim3 grid((np + gp * G - 1) / (gp * G) + (pair && dyn ? 1 : 0), yb, batch);
-    auto *m = reinterpret_cast<unsigned long long *>(mask);
+    auto *m = reinterpret_cast<unsigned long long *>(a.mask);
     const int pe = dyn ? dyn->hi : p0 + np;
     const int *ds = dyn ? dyn->start : nullptr, *dh = dyn ? dyn->hi_ptr : nullptr;
-    const int dw = dyn ? dyn->win : 0, rs = rowmap ? req_stride : Pp;
+    const int dw = dyn ? dyn->win : 0, rs = rowmap ? a.req_stride : Pp;
 #define NAS_FIT(K, GV, ...)                                                                         \
     if (el)                                                                                         \
         K##_c<GV><<<grid, FIT_THREADS, 0, st>>>(cap, N, n0, nloc, n_chunks, req, Pp, p0, pe, m, ds, \

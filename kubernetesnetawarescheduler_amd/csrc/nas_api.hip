@@ -157,6 +157,7 @@ bool valid_dtype(int dtype) {
 }
 
 // event pool for per-stage device timing on the context stream
+enum { T_FIT, T_COST, T_MERGE, T_COMMIT, T_VOTE, T_TOTAL };
 struct Timer {
     nas_ctx *ctx;
     std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> spans;
@@ -193,8 +194,16 @@ struct Timer {
         }
         return s;
     }
+    // the extended mode's stage totals into ctx->timings (zeroed by the
+    // caller): a stage the call booked no span under stays 0
+    void report_stages() {
+        ctx->timings.fit_ms = total(T_FIT);
+        ctx->timings.cost_ms = total(T_COST);
+        ctx->timings.merge_ms = total(T_MERGE);
+        ctx->timings.commit_ms = total(T_COMMIT);
+        ctx->timings.total_ms = total(T_TOTAL);
+    }
 };
-enum { T_FIT, T_COST, T_MERGE, T_COMMIT, T_VOTE, T_TOTAL };
 
 int validate_perm(const int32_t *o, int n, std::vector<int32_t> &pos) {
     pos.assign(n, -1);
@@ -431,19 +440,46 @@ int tile_pods(const nas_ctx *ctx) {
 // A launch over a main pod range (no rescore window, no row map) decides the
 // fit itself from `fit` (k_cost.hip: fused fit), so no k_fit launch sits
 // between two cost launches of a scoring stream; windows keep the k_fit mask.
-hipError_t launch_cost(nas_ctx *ctx, hipStream_t st, int Pp, int p0, int np, const uint64_t *mask,
-                       const nas::Dyn *dyn, int batch, const nas::Ovf *ov,
-                       const int32_t *rowmap = nullptr, const nas::FitSrc *fit = nullptr,
-                       bool narrow = false, uint32_t *cache = nullptr) {
-    const bool wide = !narrow && wide_ok(ctx);
-    if (ctx->dtype == NAS_DT_F32)
-        return nas::launch_cost_topk(st, NAS_DT_BF16, ctx->Lt6.p, ctx->WA6.p, ctx->Mp, 6 * ctx->Kp,
-                                     Pp, p0, np, mask, ctx->partial.as<uint64_t>(),
-                                     ctx->pbound.as<uint64_t>(), ctx->Nloc0, dyn, batch, nullptr,
-                                     rowmap, wide, fit, cache);
-    return nas::launch_cost_topk(st, ctx->dtype, ctx->Lt.p, ctx->WA.p, ctx->Mp, ctx->Kp, Pp, p0, np,
-                                 mask, ctx->partial.as<uint64_t>(), ctx->pbound.as<uint64_t>(),
-                                 ctx->Nloc0, dyn, batch, ov, rowmap, wide, fit, cache);
+// (the context's mask, partial lists, operands -- NAS_DT_F32: the bf16 splits --
+// and, unless the caller names a view's, overflow lists)
+hipError_t launch_cost(nas_ctx *ctx, hipStream_t st, const nas::CostArgs &a) {
+    const bool wide = !a.force_narrow && wide_ok(ctx);
+    const bool f32 = ctx->dtype == NAS_DT_F32;
+    const nas::Ovf ov = make_ovf(ctx);
+    return nas::launch_cost_topk(st, f32 ? NAS_DT_BF16 : ctx->dtype, f32 ? ctx->Lt6.p : ctx->Lt.p,
+                                 f32 ? ctx->WA6.p : ctx->WA.p, ctx->Mp, f32 ? 6 * ctx->Kp : ctx->Kp,
+                                 a.Pp, a.p0, a.np, ctx->mask.as<uint64_t>(),
+                                 ctx->partial.as<uint64_t>(), ctx->pbound.as<uint64_t>(), ctx->Nloc0,
+                                 a.dyn, a.batch, f32 ? nullptr : a.ovf ? a.ovf : &ov, a.rowmap, wide,
+                                 a.fit, a.cache);
+}
+
+// ---- launch arguments filled from the context's buffers (the leading fields,
+// in declaration order); a call site assigns only what distinguishes it.
+// k_fit of main pods [p0, p0 + np) against `cap`, into the context's mask
+nas::FitArgs fit_args(const nas_ctx *ctx, const int32_t *cap, int p0, int np) {
+    nas::FitArgs a{cap, ctx->N, ctx->Nloc0, ctx->Nloc, ctx->Mp, ctx->req.as<int32_t>(), ctx->Pp,
+                   p0, np, ctx->mask.as<uint64_t>()};
+    a.el = elig(ctx);
+    return a;
+}
+// n_lists source lists per pod into the context's candidate lists (the caller
+// names the pods, and another destination where it has one)
+nas::MergeArgs merge_lists(const nas_ctx *ctx, const uint64_t *keys, const uint64_t *bounds,
+                           int n_lists, int64_t stride, int64_t bstride) {
+    return {keys, bounds, n_lists, stride, bstride, ctx->cand_key.as<uint64_t>(),
+            ctx->cand_bound.as<uint64_t>()};
+}
+// ... the local merge of a cost launch's node-tile lists, rows `rows` pods apart
+nas::MergeArgs merge_partials(const nas_ctx *ctx, int rows) {
+    return merge_lists(ctx, ctx->partial.as<uint64_t>(), ctx->pbound.as<uint64_t>(),
+                       ctx->Mp / nas::COST_BM, (int64_t)rows * KC, rows);
+}
+// a commit walk over pods [p_begin, p_end) (p_begin < 0: from the halt word)
+nas::CommitArgs commit_args(const nas_ctx *ctx, int p_begin, int p_end) {
+    return {ctx->cand_key.as<uint64_t>(), ctx->cand_bound.as<uint64_t>(), ctx->req.as<int32_t>(),
+            ctx->Pp, p_begin, p_end, ctx->cap.as<int32_t>(), ctx->N, ctx->out_node.as<int32_t>(),
+            ctx->out_cost_i.as<int32_t>(), ctx->status.as<int32_t>(), zrow_ptr(ctx)};
 }
 
 // exact traffic row (n values, each within int32) -> the int8 plane row and
@@ -724,34 +760,21 @@ int exchange(nas_ctx *ctx, int ch, hipStream_t st, const uint64_t *keys, const u
     return NAS_OK;
 }
 
-// The pod arrays a scoring pass reads and writes: the context's own, or the
-// gathered scratch view of a rescore (k_rescore.hip) with its own row stride.
-struct PodView {
-    const void *WA;
-    const int32_t *req;
-    int Pp;  // row stride of req / mask / partial lists
-    uint64_t *key, *bound;
-};
-
-PodView main_view(nas_ctx *ctx) {
-    return {ctx->WA.p, ctx->req.as<int32_t>(), ctx->Pp, ctx->cand_key.as<uint64_t>(),
-            ctx->cand_bound.as<uint64_t>()};
-}
-
 // merge of pods [p_lo, p_hi)'s node-tile lists (-> exchange over `cm` and
 // merge across ranks), on stream st behind their cost launch; gbuf picks the
 // gathered-list scratch (one per stream that exchanges)
 int merge_range(nas_ctx *ctx, Timer &tm, int p_lo, int p_hi, hipStream_t st, int ch,
-                int gbuf, const PodView &v, int32_t *init_status = nullptr) {
+                int gbuf, int32_t *init_status = nullptr) {
     const int pr0 = p_lo / nas::COST_BN * nas::COST_BN;
     const int pr1 = (int)nas::round_up(p_hi, nas::COST_BN);
     const int np = pr1 - pr0;
     hipEvent_t e2 = tm.fine(st);
-    const int n_lists = ctx->Mp / nas::COST_BM;
+    nas::MergeArgs local = merge_partials(ctx, ctx->Pp);
+    local.p0 = p_lo;
+    local.np = p_hi - p_lo;
     if (!exchanging(ctx)) {
-        HIPCK(nas::launch_merge(st, ctx->partial.as<uint64_t>(), ctx->pbound.as<uint64_t>(),
-                                n_lists, (int64_t)v.Pp * KC, v.Pp, 0, p_lo, p_hi - p_lo, v.key,
-                                v.bound, 0, nullptr, 0, 1, 0, nullptr, init_status));
+        local.init_status = init_status;
+        HIPCK(nas::launch_merge(st, local));
     } else {
         if (init_status) return nas::fail(ctx, NAS_ERR_STATE, "status init rides a local merge only");
         // this rank's lists of pods [pr0, pr1) go straight into one send
@@ -761,15 +784,20 @@ int merge_range(nas_ctx *ctx, Timer &tm, int p_lo, int p_hi, hipStream_t st, int
         OK(nas::ensure(ctx, ctx->xsend[gbuf], seg * 8));
         auto *xs = ctx->xsend[gbuf].as<uint64_t>();
         auto *gx = ctx->gather[gbuf].as<uint64_t>();
-        HIPCK(nas::launch_merge(st, ctx->partial.as<uint64_t>(), ctx->pbound.as<uint64_t>(),
-                                n_lists, (int64_t)v.Pp * KC, v.Pp, 0, p_lo, p_hi - p_lo, xs,
-                                xs + (size_t)np * KC, pr0));
+        local.cand_key = xs;
+        local.cand_bound = xs + (size_t)np * KC;
+        local.dst_p0 = pr0;
+        HIPCK(nas::launch_merge(st, local));
         const GatherSeg g1{xs, gx, seg * 8};
         OK(allgather(ctx, ch, st, &g1, 1, "ncclAllGather"));
         if (ctx->rehearse > 1)
             HIPCK(nas::launch_rehearse_replicate(st, gx, seg, ctx->rehearse, ctx->N));
-        HIPCK(nas::launch_merge(st, gx, gx + (size_t)np * KC, ctx->world, (int64_t)seg,
-                                (int64_t)seg, pr0, p_lo, p_hi - p_lo, v.key, v.bound));
+        nas::MergeArgs cross = merge_lists(ctx, gx, gx + (size_t)np * KC, ctx->world, (int64_t)seg,
+                                           (int64_t)seg);
+        cross.src_p0 = pr0;
+        cross.p0 = p_lo;
+        cross.np = p_hi - p_lo;
+        HIPCK(nas::launch_merge(st, cross));
     }
     tm.span(T_MERGE, e2, tm.fine(st));
     return NAS_OK;
@@ -779,15 +807,12 @@ int merge_range(nas_ctx *ctx, Timer &tm, int p_lo, int p_hi, hipStream_t st, int
 // fit -> cost/top-k, then (merge = true) merge_range on the same stream over
 // the stream's communicator
 int score_range(nas_ctx *ctx, Timer &tm, int p_lo, int p_hi, hipStream_t st = nullptr,
-                const int32_t *cap = nullptr, const PodView *view = nullptr, bool merge = true) {
+                const int32_t *cap = nullptr, bool merge = true) {
     if (!st) st = ctx->stream;
     if (!cap) cap = ctx->cap.as<int32_t>();
-    const PodView v = view ? *view : main_view(ctx);
     const int sidx = st == ctx->stream2 ? 1 : 0;
     const int pr0 = p_lo / nas::COST_BN * nas::COST_BN;
     const int pr1 = (int)nas::round_up(p_hi, nas::COST_BN);
-    const int np = pr1 - pr0;
-    auto *mask = ctx->mask.as<uint64_t>();
     // the cost launch decides the fit itself (fused fit): no k_fit before it.
     // Node shards fuse too since they run the wide tile on CU-masked streams
     // (round 4): the commit stream's merge / exchange / commit kernels have
@@ -800,22 +825,24 @@ int score_range(nas_ctx *ctx, Timer &tm, int p_lo, int p_hi, hipStream_t st = nu
     // writes the mask and the 256 x 256 tile reads it, at world 1 and on shards.
     const nas::Elig *el = elig(ctx);
     const bool fuse = !el && (ctx->world == 1 || wide_ok(ctx));
-    const nas::FitSrc fit{cap, v.req, ctx->N, ctx->Nloc0, ctx->Nloc};
+    const nas::FitSrc fit{cap, ctx->req.as<int32_t>(), ctx->N, ctx->Nloc0, ctx->Nloc};
     hipEvent_t e0 = tm.fine(st);
-    if (!fuse)
-        HIPCK(nas::launch_fit(st, cap, ctx->N, ctx->Nloc0, ctx->Nloc, ctx->Mp, v.req, p_hi, v.Pp,
-                              p_lo, p_hi - p_lo, mask, nullptr, 1, nullptr, 0, el));
+    if (!fuse) HIPCK(nas::launch_fit(st, fit_args(ctx, cap, p_lo, p_hi - p_lo)));
     hipEvent_t e1 = fuse ? e0 : tm.fine(st);
-    const nas::Ovf ov = make_ovf(ctx);
+    nas::CostArgs ca;
+    ca.Pp = ctx->Pp;
+    ca.p0 = pr0;
+    ca.np = pr1 - pr0;
+    ca.fit = fuse ? &fit : nullptr;
+    ca.force_narrow = el != nullptr;
     // (a pass with the cost-row cache: the main launches store every cost too)
-    uint32_t *cache = ctx->cache_active && !view ? ctx->cost_cache.as<uint32_t>() : nullptr;
-    HIPCK(launch_cost(ctx, st, v.Pp, pr0, np, mask, nullptr, 1, &ov, nullptr, fuse ? &fit : nullptr,
-                      el != nullptr, cache));
+    ca.cache = ctx->cache_active ? ctx->cost_cache.as<uint32_t>() : nullptr;
+    HIPCK(launch_cost(ctx, st, ca));
     hipEvent_t e2 = tm.fine(st);
     tm.span(T_FIT, e0, e1);
     tm.span(T_COST, e1, e2);
     ctx->timings.cost_launches += 1;
-    if (merge) OK(merge_range(ctx, tm, p_lo, p_hi, st, sidx ? CH_SCORE2 : CH_SCORE, sidx, v));
+    if (merge) OK(merge_range(ctx, tm, p_lo, p_hi, st, sidx ? CH_SCORE2 : CH_SCORE, sidx));
     return NAS_OK;
 }
 
@@ -855,68 +882,59 @@ int gathered_slot(nas_ctx *ctx, Timer &tm, hipStream_t st, int ch, int32_t *pub,
     const bool xch = exchanging(ctx);
     auto *ck = ctx->cand_key.as<uint64_t>();
     auto *cbnd = ctx->cand_bound.as<uint64_t>();
+    const nas::Dyn dyn{ctl, R, 0, ctl + 1};
+    hipEvent_t e1 = tm.fine(st), e3 = nullptr;
+    // either way the fresh lists go straight into the pods' own list slots
+    // (idx) -- or, with an exchange, into the view rows first
     if (ctx->cache_active) {
         // the pods' costs are in the cost-row cache: each view row's list from
-        // its cached row against the capacity now (k_rescore_cached), straight
-        // into the pod's own slot -- or into the view rows for the exchange
-        hipEvent_t e1 = tm.fine(st);
+        // its cached row against the capacity now (k_rescore_cached)
         HIPCK(nas::launch_rescore_cached(st, ctx->cost_cache.as<uint32_t>(), ctx->Mp, ctx->Nloc,
                                          ctx->Nloc0, ctx->cap.as<int32_t>(), ctx->N,
                                          ctx->req.as<int32_t>(), ctx->Pp, idx, ctl, R,
                                          xch ? gk : ck, xch ? gb : cbnd, xch));
-        hipEvent_t e3 = tm.fine(st);
-        nas::Dyn dyn{ctl, R, 0, ctl + 1};
-        if (xch) {
-            OK(nas::ensure(ctx, ctx->g_gk, (size_t)ctx->world * R * KC * 8));
-            OK(nas::ensure(ctx, ctx->g_gb, (size_t)ctx->world * R * 8));
-            auto *xk = ctx->g_gk.as<uint64_t>();
-            auto *xb = ctx->g_gb.as<uint64_t>();
-            OK(exchange(ctx, ch, st, gk, gb, (size_t)R, xk, xb));
-            HIPCK(nas::launch_merge(st, xk, xb, ctx->world, (int64_t)R * KC, R, 0, 0, 0, ck, cbnd, 0,
-                                    &dyn, 0, 1, 0, idx));
-        }
-        hipEvent_t e4 = tm.fine(st);
-        HIPCK(nas::launch_commit(st, ck, cbnd, ctx->req.as<int32_t>(), ctx->Pp, -1, hi,
-                                 ctx->cap.as<int32_t>(), ctx->N, ctx->out_node.as<int32_t>(),
-                                 ctx->out_cost_i.as<int32_t>(), halt, 1, pub, zrow_ptr(ctx)));
+        e3 = tm.fine(st);
         tm.span(T_COST, e1, e3);
-        tm.span(T_MERGE, e3, e4);
-        tm.span(T_COMMIT, e0, e1);
-        tm.span(T_COMMIT, e4, tm.fine(st));
-        return NAS_OK;
+    } else {
+        nas::FitArgs fa = fit_args(ctx, ctx->cap.as<int32_t>(), 0, R);
+        fa.Pp = R;
+        fa.dyn = &dyn;
+        fa.rowmap = idx;
+        fa.req_stride = ctx->Pp;
+        HIPCK(nas::launch_fit(st, fa));
+        hipEvent_t e2 = tm.fine(st);
+        const nas::Ovf ov = make_ovf(ctx, idx, ctl + 1);  // view row r is pod idx[r]
+        nas::CostArgs ca;
+        ca.Pp = R;
+        ca.dyn = &dyn;
+        ca.ovf = &ov;
+        ca.rowmap = idx;
+        HIPCK(launch_cost(ctx, st, ca));
+        e3 = tm.fine(st);
+        nas::MergeArgs local = merge_partials(ctx, R);
+        local.dyn = &dyn;
+        local.cand_key = xch ? gk : ck;
+        local.cand_bound = xch ? gb : cbnd;
+        local.dst_idx = xch ? nullptr : idx;
+        HIPCK(nas::launch_merge(st, local));
+        tm.span(T_FIT, e1, e2);
+        tm.span(T_COST, e2, e3);
     }
-    nas::Dyn dyn{ctl, R, 0, ctl + 1};
-    auto *mask = ctx->mask.as<uint64_t>();
-    hipEvent_t e1 = tm.fine(st);
-    HIPCK(nas::launch_fit(st, ctx->cap.as<int32_t>(), ctx->N, ctx->Nloc0, ctx->Nloc, ctx->Mp,
-                          ctx->req.as<int32_t>(), R, R, 0, R, mask, &dyn, 1, idx, ctx->Pp,
-                          elig(ctx)));
-    hipEvent_t e2 = tm.fine(st);
-    const nas::Ovf ov = make_ovf(ctx, idx, ctl + 1);  // view row r is pod idx[r]
-    HIPCK(launch_cost(ctx, st, R, 0, 0, mask, &dyn, 1, &ov, idx));
-    hipEvent_t e3 = tm.fine(st);
-    const int n_lists = ctx->Mp / nas::COST_BM;
-    // the last merge writes the fresh lists straight into the pods' own list
-    // slots (idx); with an exchange, the local merge first fills the view
-    HIPCK(nas::launch_merge(st, ctx->partial.as<uint64_t>(), ctx->pbound.as<uint64_t>(), n_lists,
-                            (int64_t)R * KC, R, 0, 0, 0, xch ? gk : ck, xch ? gb : cbnd, 0, &dyn,
-                            0, 1, 0, xch ? nullptr : idx));
     if (xch) {
         OK(nas::ensure(ctx, ctx->g_gk, (size_t)ctx->world * R * KC * 8));
         OK(nas::ensure(ctx, ctx->g_gb, (size_t)ctx->world * R * 8));
         auto *xk = ctx->g_gk.as<uint64_t>();
         auto *xb = ctx->g_gb.as<uint64_t>();
         OK(exchange(ctx, ch, st, gk, gb, (size_t)R, xk, xb));
-        HIPCK(nas::launch_merge(st, xk, xb, ctx->world, (int64_t)R * KC, R, 0, 0, 0, ck, cbnd, 0,
-                                &dyn, 0, 1, 0, idx));
+        nas::MergeArgs cross = merge_lists(ctx, xk, xb, ctx->world, (int64_t)R * KC, R);
+        cross.dyn = &dyn;
+        cross.dst_idx = idx;
+        HIPCK(nas::launch_merge(st, cross));
     }
     hipEvent_t e4 = tm.fine(st);
-    HIPCK(nas::launch_commit(st, ctx->cand_key.as<uint64_t>(), ctx->cand_bound.as<uint64_t>(),
-                             ctx->req.as<int32_t>(), ctx->Pp, -1, hi, ctx->cap.as<int32_t>(),
-                             ctx->N, ctx->out_node.as<int32_t>(), ctx->out_cost_i.as<int32_t>(),
-                             halt, 1, pub, zrow_ptr(ctx)));
-    tm.span(T_FIT, e1, e2);
-    tm.span(T_COST, e2, e3);
+    nas::CommitArgs cm = commit_args(ctx, -1, hi);
+    cm.pub = pub;
+    HIPCK(nas::launch_commit(st, cm));
     tm.span(T_MERGE, e3, e4);
     tm.span(T_COMMIT, e0, e1);
     tm.span(T_COMMIT, e4, tm.fine(st));
@@ -934,46 +952,30 @@ int no_batch(nas_ctx *ctx, const char *what) {
     return NAS_OK;
 }
 
-// A rescore slot on the commit stream, enqueued behind a chunk's commit: if
-// the walk halted at pod s (halt word), rescore pods [s, min(s + RESCORE_PODS,
-// hi)) against the working capacity and resume the walk from s to hi; if it
-// did not halt, every kernel exits at once (the exchange still runs, so all
-// ranks issue the same collectives).  Every pod of [s, hi) belongs to chunks
-// whose scoring the commit stream has already waited for: no other stream
-// touches their masks, partial lists or candidate lists.
-int rescore_slot(nas_ctx *ctx, hipStream_t sc, int hi, int32_t *pub = nullptr) {
-    int32_t *halt = ctx->status.as<int32_t>();
-    const nas::Dyn dyn{halt, RESCORE_PODS, hi};
-    const int B = ctx->B;  // batched: every cluster with a stop gets its own window
-    auto *mask = ctx->mask.as<uint64_t>();
-    HIPCK(nas::launch_fit(sc, ctx->cap.as<int32_t>(), ctx->N, ctx->Nloc0, ctx->Nloc, ctx->Mp,
-                          ctx->req.as<int32_t>(), ctx->P, ctx->Pp, 0, RESCORE_PODS, mask, &dyn, B,
-                          nullptr, 0, elig(ctx)));
-    const nas::Ovf ov = make_ovf(ctx);
-    HIPCK(launch_cost(ctx, sc, ctx->Pp, 0, 0, mask, &dyn, B, &ov));
-    const int n_lists = ctx->Mp / nas::COST_BM;
-    if (!exchanging(ctx)) {
-        HIPCK(nas::launch_merge(sc, ctx->partial.as<uint64_t>(), ctx->pbound.as<uint64_t>(),
-                                n_lists, (int64_t)ctx->Pp * KC, ctx->Pp, 0, 0, 0,
-                                ctx->cand_key.as<uint64_t>(), ctx->cand_bound.as<uint64_t>(), 0,
-                                &dyn, 0, B, ctx->Pp));
-    } else {
-        auto *rk = ctx->resc_key.as<uint64_t>();
-        auto *rb = ctx->resc_bound.as<uint64_t>();
-        auto *gk = ctx->gather_r.as<uint64_t>();
-        auto *gb = ctx->gbound_r.as<uint64_t>();
-        HIPCK(nas::launch_merge(sc, ctx->partial.as<uint64_t>(), ctx->pbound.as<uint64_t>(),
-                                n_lists, (int64_t)ctx->Pp * KC, ctx->Pp, 0, 0, 0, rk, rb, 0, &dyn,
-                                nas::MERGE_DST_WINDOW));
-        OK(exchange(ctx, CH_COMMIT, sc, rk, rb, RESCORE_PODS, gk, gb));
-        HIPCK(nas::launch_merge(sc, gk, gb, ctx->world, (int64_t)RESCORE_PODS * KC, RESCORE_PODS,
-                                0, 0, 0, ctx->cand_key.as<uint64_t>(),
-                                ctx->cand_bound.as<uint64_t>(), 0, &dyn, nas::MERGE_SRC_WINDOW));
-    }
-    HIPCK(nas::launch_commit(sc, ctx->cand_key.as<uint64_t>(), ctx->cand_bound.as<uint64_t>(),
-                             ctx->req.as<int32_t>(), ctx->Pp, -1, hi, ctx->cap.as<int32_t>(),
-                             ctx->N, ctx->out_node.as<int32_t>(), ctx->out_cost_i.as<int32_t>(),
-                             halt, B, pub, zrow_ptr(ctx)));
+// A batch's rescore slot (place_batch; a cluster batch has no node shards, so
+// nothing is exchanged): every cluster whose walk halted at a pod s (its halt
+// word) gets its own window -- pods [s, min(s + RESCORE_PODS, hi)) are rescored
+// against the working capacity and the walk resumes from s to hi; a cluster
+// that did not halt costs workgroups that exit at once.
+int rescore_slot(nas_ctx *ctx, hipStream_t st, int hi) {
+    const nas::Dyn dyn{ctx->status.as<int32_t>(), RESCORE_PODS, hi};
+    nas::FitArgs fa = fit_args(ctx, ctx->cap.as<int32_t>(), 0, RESCORE_PODS);
+    fa.dyn = &dyn;
+    fa.batch = ctx->B;
+    HIPCK(nas::launch_fit(st, fa));
+    nas::CostArgs ca;
+    ca.Pp = ctx->Pp;
+    ca.dyn = &dyn;
+    ca.batch = ctx->B;
+    HIPCK(launch_cost(ctx, st, ca));
+    nas::MergeArgs ma = merge_partials(ctx, ctx->Pp);
+    ma.dyn = &dyn;
+    ma.batch = ctx->B;
+    ma.dst_cluster_pods = ctx->Pp;
+    HIPCK(nas::launch_merge(st, ma));
+    nas::CommitArgs cm = commit_args(ctx, -1, hi);
+    cm.batch = ctx->B;
+    HIPCK(nas::launch_commit(st, cm));
     return NAS_OK;
 }
 
@@ -983,23 +985,34 @@ int rescore_slot(nas_ctx *ctx, hipStream_t sc, int hi, int32_t *pub = nullptr) {
 int score_batch(nas_ctx *ctx, Timer &tm) {
     hipStream_t st = ctx->stream;
     const int B = ctx->B, P = ctx->P, Pp = ctx->Pp, N = ctx->N;
-    auto *mask = ctx->mask.as<uint64_t>();
     hipEvent_t e0 = tm.mark(st);
     hipEvent_t e1 = e0;
-    const nas::Ovf ov = make_ovf(ctx);
     const nas::FitSrc fit{ctx->cap.as<int32_t>(), ctx->req.as<int32_t>(), N, 0, N};
+    nas::CostArgs ca;
+    ca.Pp = Pp;
+    ca.batch = B;
+    ca.fit = &fit;
     // whole wide tiles (384 pods) over the pods a multiple of 768 (a launch
     // covers 256-pod units) reaches, 256 x 256 tiles over the rest: C5's 5,000
     // pods (Pp 5,120) are 12 wide + 2 narrow tiles per cluster instead of 14
     // wide ones, the last of them 8 pods of 384
     const int W = tile_pods(ctx) != nas::COST_BN ? Pp / 768 * 768 : 0;
-    if (W > 0) HIPCK(launch_cost(ctx, st, Pp, 0, W, mask, nullptr, B, &ov, nullptr, &fit));
-    if (W < Pp) HIPCK(launch_cost(ctx, st, Pp, W, Pp - W, mask, nullptr, B, &ov, nullptr, &fit, true));
+    if (W > 0) {
+        ca.np = W;
+        HIPCK(launch_cost(ctx, st, ca));
+    }
+    if (W < Pp) {
+        ca.p0 = W;
+        ca.np = Pp - W;
+        ca.force_narrow = true;
+        HIPCK(launch_cost(ctx, st, ca));
+    }
     hipEvent_t e2 = tm.mark(st);
-    const int n_lists = ctx->Mp / nas::COST_BM;
-    HIPCK(nas::launch_merge(st, ctx->partial.as<uint64_t>(), ctx->pbound.as<uint64_t>(), n_lists,
-                            (int64_t)Pp * KC, Pp, 0, 0, P, ctx->cand_key.as<uint64_t>(),
-                            ctx->cand_bound.as<uint64_t>(), 0, nullptr, 0, B, Pp));
+    nas::MergeArgs ma = merge_partials(ctx, Pp);
+    ma.np = P;
+    ma.batch = B;
+    ma.dst_cluster_pods = Pp;
+    HIPCK(nas::launch_merge(st, ma));
     tm.span(T_FIT, e0, e1);
     tm.span(T_COST, e1, e2);
     tm.span(T_MERGE, e2, tm.mark(st));
@@ -1014,7 +1027,7 @@ int score_batch(nas_ctx *ctx, Timer &tm) {
 int place_batch(nas_ctx *ctx, Timer &tm, int32_t *node_out, float *cost_out,
                 int64_t *int_score_out) {
     hipStream_t st = ctx->stream;
-    const int B = ctx->B, P = ctx->P, Pp = ctx->Pp, N = ctx->N;
+    const int B = ctx->B, P = ctx->P, Pp = ctx->Pp;
     int32_t *halt = ctx->status.as<int32_t>();
     int32_t *hs = ctx->host_status.as<int32_t>();
     hipEvent_t t0 = tm.mark(st);
@@ -1031,10 +1044,11 @@ int place_batch(nas_ctx *ctx, Timer &tm, int32_t *node_out, float *cost_out,
     int32_t *stage = reinterpret_cast<int32_t *>(ctx->host_status.as<char>() + host_out_offset(ctx->B));
     const size_t BP = (size_t)B * P;
     const bool want_raw = cost_out || int_score_out;
-    HIPCK(nas::launch_commit(st, ctx->cand_key.as<uint64_t>(), ctx->cand_bound.as<uint64_t>(),
-                             ctx->req.as<int32_t>(), Pp, 0, P, ctx->cap.as<int32_t>(), N,
-                             ctx->out_node.as<int32_t>(), ctx->out_cost_i.as<int32_t>(), halt, B,
-                             nullptr, zrow_ptr(ctx), stage, want_raw ? stage + BP : nullptr));
+    nas::CommitArgs cm = commit_args(ctx, 0, P);
+    cm.batch = B;
+    cm.stage_node = stage;
+    cm.stage_cost = want_raw ? stage + BP : nullptr;
+    HIPCK(nas::launch_commit(st, cm));
     tm.span(T_COMMIT, e3, tm.mark(st));
     auto fetch = [&]() -> int {
         HIPCK(hipMemcpy2DAsync(stage, (size_t)P * 4, ctx->out_node.p, (size_t)Pp * 4,
@@ -1074,11 +1088,7 @@ int place_batch(nas_ctx *ctx, Timer &tm, int32_t *node_out, float *cost_out,
         rounds += hs[b * nas::STATUS_INTS + 2];
     }
     unpack_range(node_out, cost_out, int_score_out, stage, stage + BP, 0, (int)BP, ctx->dtype, unsched);
-    ctx->timings.fit_ms = tm.total(T_FIT);
-    ctx->timings.cost_ms = tm.total(T_COST);
-    ctx->timings.merge_ms = tm.total(T_MERGE);
-    ctx->timings.commit_ms = tm.total(T_COMMIT);
-    ctx->timings.total_ms = tm.total(T_TOTAL);
+    tm.report_stages();
     ctx->timings.rescore_rounds = dev_rounds;
     ctx->timings.unschedulable = unsched;
     ctx->timings.commit_rounds = rounds;
@@ -1349,16 +1359,9 @@ int alloc_extended(nas_ctx *ctx) {
         HIPCK(hipMemset(ctx->commit_flag.p, 0, 8));
         ctx->commit_seq = 0;
     }
-    if (exchanging(ctx)) {
-        for (int i = 0; i < 3; ++i) {
+    if (exchanging(ctx))
+        for (int i = 0; i < 3; ++i)
             OK(nas::ensure(ctx, ctx->gather[i], (size_t)ctx->world * ctx->Pp * (KC + 1) * 8));
-            OK(nas::ensure(ctx, ctx->gbound[i], (size_t)ctx->world * ctx->Pp * 8));
-        }
-        OK(nas::ensure(ctx, ctx->resc_key, (size_t)RESCORE_PODS * KC * 8));
-        OK(nas::ensure(ctx, ctx->resc_bound, (size_t)RESCORE_PODS * 8));
-        OK(nas::ensure(ctx, ctx->gather_r, (size_t)ctx->world * RESCORE_PODS * KC * 8));
-        OK(nas::ensure(ctx, ctx->gbound_r, (size_t)ctx->world * RESCORE_PODS * 8));
-    }
     // pinned: the status words, then (from host_out_offset(B)) a staging area
     // for the placements and scores so their copies back are DMA, not staged,
     // and a second one for nas_place's speculative full copy (below)
@@ -1671,9 +1674,7 @@ void nas_destroy(nas_ctx *ctx) {
                       &ctx->pod_snap, &ctx->best, &ctx->winners, &ctx->snap_best, &ctx->snap_win,
                       &ctx->Lt, &ctx->WA, &ctx->cap0, &ctx->cap, &ctx->cap_snap, &ctx->req, &ctx->mask,
                       &ctx->partial, &ctx->pbound, &ctx->cand_key, &ctx->cand_bound,
-                      &ctx->gather[0], &ctx->gbound[0], &ctx->gather[1], &ctx->gbound[1],
-                      &ctx->gather[2], &ctx->gbound[2], &ctx->xsend[2],
-                      &ctx->resc_key, &ctx->resc_bound, &ctx->gather_r, &ctx->gbound_r,
+                      &ctx->gather[0], &ctx->gather[1], &ctx->gather[2], &ctx->xsend[2],
                       &ctx->out_node, &ctx->out_cost_f, &ctx->out_cost_i,
                       &ctx->g_words, &ctx->g_idx, &ctx->g_key,
                       &ctx->g_bound, &ctx->g_gk, &ctx->g_gb, &ctx->status, &ctx->scratch,
@@ -2446,9 +2447,7 @@ int nas_filter(nas_ctx *ctx, uint64_t *mask_out) {
     OK(prepare_constraints(ctx));
     Timer tm(ctx);
     hipEvent_t a = tm.mark();
-    HIPCK(nas::launch_fit(ctx->stream, ctx->cap.as<int32_t>(), ctx->N, ctx->Nloc0, ctx->Nloc,
-                          ctx->Mp, ctx->req.as<int32_t>(), ctx->P, ctx->Pp, 0, ctx->P,
-                          ctx->mask.as<uint64_t>(), nullptr, 1, nullptr, 0, elig(ctx)));
+    HIPCK(nas::launch_fit(ctx->stream, fit_args(ctx, ctx->cap.as<int32_t>(), 0, ctx->P)));
     hipEvent_t b = tm.mark();
     if (mask_out) {
         const int chunks = (ctx->Nloc + 63) / 64;
@@ -2461,10 +2460,9 @@ int nas_filter(nas_ctx *ctx, uint64_t *mask_out) {
     return NAS_OK;
 }
 
-int nas_score(nas_ctx *ctx) {
-    NAS_RANGE("nas_score");
-    OK(bind(ctx));
-    OK(check_extended(ctx));
+// a scoring pass without commits (nas_score, nas_score_range): pods [p_lo, p_hi)
+// of the cluster, or every cluster of a batch
+static int score_only(nas_ctx *ctx, int p_lo, int p_hi) {
     OK(alloc_extended(ctx));
     OK(prepare_ovf(ctx));
     OK(prepare_split(ctx));
@@ -2473,14 +2471,19 @@ int nas_score(nas_ctx *ctx) {
     std::memset(&ctx->timings, 0, sizeof(ctx->timings));
     Timer tm(ctx);
     if (ctx->B > 1) OK(score_batch(ctx, tm));
-    else OK(score_range(ctx, tm, 0, ctx->P));
+    else OK(score_range(ctx, tm, p_lo, p_hi));
     if (has_coll(ctx)) inject_stall(ctx, ctx->stream);
     OK(sync_stream(ctx, ctx->stream));
-    ctx->timings.fit_ms = tm.total(T_FIT);
-    ctx->timings.cost_ms = tm.total(T_COST);
-    ctx->timings.merge_ms = tm.total(T_MERGE);
+    tm.report_stages();  // (no commit, no pass total: those stay 0)
     ctx->scored = true;
     return NAS_OK;
+}
+
+int nas_score(nas_ctx *ctx) {
+    NAS_RANGE("nas_score");
+    OK(bind(ctx));
+    OK(check_extended(ctx));
+    return score_only(ctx, 0, ctx->P);
 }
 
 namespace {
@@ -2636,6 +2639,19 @@ int nas_place(nas_ctx *ctx, int32_t *node_out, float *cost_out, int64_t *int_sco
         ctx->opt_commit_wait_ms > 0 ? ctx->opt_commit_wait_ms
         : has_coll(ctx)             ? (ctx->opt_comm_timeout_ms > 0 ? ctx->opt_comm_timeout_ms : 600000)
                                     : 2000;
+    // a chunk's commit (both plans): the walk stages the chunk's rows itself;
+    // the pass's last commit also writes the status words into the pinned
+    // host area when nothing follows it (no speculative slots): the host
+    // then waits for that commit alone, with no status copy behind it
+    auto commit_chunk = [&](hipStream_t s, int lo, int hi, bool last) -> int {
+        nas::CommitArgs cm = commit_args(ctx, lo, hi);
+        cm.pub = pub;
+        cm.stage_node = stage;
+        cm.stage_cost = want_raw ? stage + P : nullptr;
+        cm.stage_status = last && status_in_commit ? hs : nullptr;
+        HIPCK(nas::launch_commit(s, cm));
+        return NAS_OK;
+    };
     if (herd) {
         // The herd plan: chunks of one wave of cost workgroups, scored and
         // merged back to back on one stream; each chunk's commit and
@@ -2657,15 +2673,11 @@ int nas_place(nas_ctx *ctx, int32_t *node_out, float *cost_out, int64_t *int_sco
             // (the merge on the scoring stream, behind its cost launch, with
             // the whole GPU: ~10 us; on the commit stream's leftover CUs it
             // took ~60 us, and the commit stream fell behind the scoring)
-            OK(score_range(ctx, tm, lo, hi, st, score_cap, nullptr, false));
-            OK(merge_range(ctx, tm, lo, hi, st, CH_SCORE, 0, main_view(ctx)));
+            OK(score_range(ctx, tm, lo, hi, st, score_cap, false));
+            OK(merge_range(ctx, tm, lo, hi, st, CH_SCORE, 0));
             HIPCK(hipStreamWaitEvent(sc, tm.mark(st), 0));
             hipEvent_t c0 = tm.fine(sc);
-            HIPCK(nas::launch_commit(sc, ctx->cand_key.as<uint64_t>(), ctx->cand_bound.as<uint64_t>(),
-                                     ctx->req.as<int32_t>(), ctx->Pp, lo, hi, ctx->cap.as<int32_t>(),
-                                     N, ctx->out_node.as<int32_t>(), ctx->out_cost_i.as<int32_t>(),
-                                     halt, 1, pub, zrow_ptr(ctx), stage, want_raw ? stage + P : nullptr,
-                                     last && status_in_commit ? hs : nullptr));
+            OK(commit_chunk(sc, lo, hi, last));
             tm.span(T_COMMIT, c0, tm.fine(sc));
             // a walk halted in this chunk resumes here, before the chunk after
             // next is scored (a halt they leave is resumed by a later chunk's
@@ -2692,7 +2704,7 @@ int nas_place(nas_ctx *ctx, int32_t *node_out, float *cost_out, int64_t *int_sco
         // ever waits behind a merge or an all-gather
         for (size_t c = 0; c < chunks.size(); ++c) {
             hipStream_t ss = ss2[c & 1];
-            OK(score_range(ctx, tm, chunks[c].first, chunks[c].second, ss, score_cap, nullptr, false));
+            OK(score_range(ctx, tm, chunks[c].first, chunks[c].second, ss, score_cap, false));
             // (one stream: nothing waits on it -- every event record or wait is a
             // packet the queue processes between two kernels)
             scored[c] = one_stream ? nullptr : tm.mark(ss);
@@ -2742,12 +2754,11 @@ int nas_place(nas_ctx *ctx, int32_t *node_out, float *cost_out, int64_t *int_sco
             if (xs_mode) {
                 if (tail) {
                     cs = ss2[c & 1];
-                    OK(merge_range(ctx, tm, lo, hi, cs, (c & 1) ? CH_SCORE2 : CH_SCORE, (int)(c & 1),
-                                   main_view(ctx)));
+                    OK(merge_range(ctx, tm, lo, hi, cs, (c & 1) ? CH_SCORE2 : CH_SCORE, (int)(c & 1)));
                     OK(after_commits(cs));
                 } else {
                     HIPCK(hipStreamWaitEvent(sx, scored[c], 0));
-                    OK(merge_range(ctx, tm, lo, hi, sx, CH_COMMIT, 2, main_view(ctx)));
+                    OK(merge_range(ctx, tm, lo, hi, sx, CH_COMMIT, 2));
                     HIPCK(hipStreamWaitEvent(sc, tm.mark(sx), 0));
                 }
             } else {
@@ -2760,18 +2771,10 @@ int nas_place(nas_ctx *ctx, int32_t *node_out, float *cost_out, int64_t *int_sco
                 // (merging the tail chunk locally before this wait, gated before
                 // its exchange / commit, measured within noise at G = 1 and 8:
                 // profiles/r04_ab_tail.txt)
-                OK(merge_range(ctx, tm, lo, hi, cs, CH_COMMIT, 0, main_view(ctx),
-                               init_in_merge ? halt : nullptr));
+                OK(merge_range(ctx, tm, lo, hi, cs, CH_COMMIT, 0, init_in_merge ? halt : nullptr));
             }
             hipEvent_t c0 = tm.fine(cs);
-            // the pass's last commit also writes the status words into the pinned
-            // host area when nothing follows it (no speculative slots): the host
-            // then waits for that commit alone, with no status copy behind it
-            HIPCK(nas::launch_commit(cs, ctx->cand_key.as<uint64_t>(), ctx->cand_bound.as<uint64_t>(),
-                                     ctx->req.as<int32_t>(), ctx->Pp, lo, hi, ctx->cap.as<int32_t>(), N,
-                                     ctx->out_node.as<int32_t>(), ctx->out_cost_i.as<int32_t>(), halt,
-                                     1, pub, zrow_ptr(ctx), stage, want_raw ? stage + P : nullptr,
-                                     last && status_in_commit ? hs : nullptr));
+            OK(commit_chunk(cs, lo, hi, last));
             // (releases the tail chunk's commit)
             if (!one_stream && !last) {
                 if (c + 2 == chunks.size() && ctx->opt_inject_commit_stall_ms > 0) {
@@ -2898,11 +2901,7 @@ int nas_place(nas_ctx *ctx, int32_t *node_out, float *cost_out, int64_t *int_sco
         }
     }
     tm.span(T_TOTAL, t0, t1);
-    ctx->timings.fit_ms = tm.total(T_FIT);
-    ctx->timings.cost_ms = tm.total(T_COST);
-    ctx->timings.merge_ms = tm.total(T_MERGE);
-    ctx->timings.commit_ms = tm.total(T_COMMIT);
-    ctx->timings.total_ms = tm.total(T_TOTAL);
+    tm.report_stages();
     ctx->timings.rescore_rounds = hs[1];
     ctx->timings.rescored_pods = hs[RESCORED];
     ctx->timings.unschedulable = unsched;
@@ -2959,21 +2958,7 @@ int nas_score_range(nas_ctx *ctx, int32_t p_lo, int32_t p_hi) {
     OK(check_extended(ctx));
     if (p_lo < 0 || p_hi > ctx->P || p_lo >= p_hi)
         return nas::fail(ctx, NAS_ERR_ARG, "nas_score_range: pod range");
-    OK(alloc_extended(ctx));
-    OK(prepare_ovf(ctx));
-    OK(prepare_split(ctx));
-    OK(prepare_zrow(ctx));
-    OK(prepare_constraints(ctx));
-    std::memset(&ctx->timings, 0, sizeof(ctx->timings));
-    Timer tm(ctx);
-    OK(score_range(ctx, tm, p_lo, p_hi));
-    if (has_coll(ctx)) inject_stall(ctx, ctx->stream);
-    OK(sync_stream(ctx, ctx->stream));
-    ctx->timings.fit_ms = tm.total(T_FIT);
-    ctx->timings.cost_ms = tm.total(T_COST);
-    ctx->timings.merge_ms = tm.total(T_MERGE);
-    ctx->scored = true;
-    return NAS_OK;
+    return score_only(ctx, p_lo, p_hi);
 }
 
 static int keys_range_ok(nas_ctx *ctx, int32_t p_lo, int32_t n, const void *keys,
@@ -3049,10 +3034,7 @@ int nas_commit(nas_ctx *ctx, int32_t p_begin, int32_t *node_out, float *cost_out
     HIPCK(hipMemsetAsync(halt, 0xff, 4, st));
     HIPCK(hipMemsetAsync(halt + 1, 0, 8, st));
     hipEvent_t c0 = tm.mark(st);
-    HIPCK(nas::launch_commit(st, ctx->cand_key.as<uint64_t>(), ctx->cand_bound.as<uint64_t>(),
-                             ctx->req.as<int32_t>(), ctx->Pp, p_begin, P, ctx->cap.as<int32_t>(),
-                             ctx->N, ctx->out_node.as<int32_t>(), ctx->out_cost_i.as<int32_t>(),
-                             halt, 1, nullptr, zrow_ptr(ctx)));
+    HIPCK(nas::launch_commit(st, commit_args(ctx, p_begin, P)));
     tm.span(T_COMMIT, c0, tm.mark(st));
     int32_t *hs = ctx->host_status.as<int32_t>();
     HIPCK(hipMemcpyAsync(hs, halt, 12, hipMemcpyDeviceToHost, st));
@@ -3076,7 +3058,7 @@ int nas_commit(nas_ctx *ctx, int32_t p_begin, int32_t *node_out, float *cost_out
                                              ? 0 : (int64_t)(int32_t)(raw[i] ^ 0x80000000u);
     }
     *stop_out = stop;
-    ctx->timings.commit_ms = tm.total(T_COMMIT);
+    tm.report_stages();  // (only the commit booked a span)
     ctx->timings.commit_rounds = hs[2];
     return NAS_OK;
 }

@@ -179,10 +179,8 @@ struct nas_ctx {
     nas::DevBuf pbound;      // [Mp/BM][Pp] uint64 exactness bound per node tile
     nas::DevBuf cand_key;    // [Pp][KC] uint64 (global node ids), after merge
     nas::DevBuf cand_bound;  // [Pp] uint64
-    nas::DevBuf gather[3];   // per scoring stream: [world][chunk][KC] uint64 (multi-GPU exchange)
-    nas::DevBuf gbound[3];   // per scoring stream: [world][chunk] uint64
-    nas::DevBuf resc_key, resc_bound;      // rescore slot staging [win][KC] / [win] (multi-GPU)
-    nas::DevBuf gather_r, gbound_r;        // rescore slot exchange [world][win][KC] / [world][win]
+    // per scoring stream (multi-GPU exchange): [world] x ([chunk][KC] keys | [chunk] bounds)
+    nas::DevBuf gather[3];
     nas::DevBuf out_node, out_cost_f, out_cost_i;  // [Pp]
     nas::DevBuf g_words, g_idx;            // gathered rescore: dry-pod ballots, indices + count
     nas::DevBuf g_key, g_bound;  // gathered rescore view's lists (rows read in place, row map g_idx)
@@ -311,18 +309,110 @@ struct Dyn {
     int hi;
     const int32_t *hi_ptr = nullptr;  // when set, hi is read on the device (per cluster)
 };
-constexpr int MERGE_SRC_WINDOW = 1;  // k_merge source lists indexed from the window start
-constexpr int MERGE_DST_WINDOW = 2;  // k_merge destination indexed from the window start
 
-// rowmap (gathered rescore view, batch 1): view row q is pod rowmap[q] -- its
-// requests (k_fit, main array with row stride req_stride) and traffic row
-// (k_cost_topk, main WA) are read in place, no gathered copy
-hipError_t launch_fit(hipStream_t st, const int32_t *cap, int N, int n0, int nloc, int Mp,
-                      const int32_t *req, int P, int Pp, int p0, int np, uint64_t *mask,
-                      const Dyn *dyn = nullptr, int batch = 1, const int32_t *rowmap = nullptr,
-                      int req_stride = 0, const Elig *el = nullptr);
-// el (batch 1): the constrained kernels -- pod p's words are el->require[p] /
-// el->tolerate[p] of the main pod array (a view's row q: pod rowmap[q])
+// ---- the launch boundary of a placement pass: launch_fit, launch_merge and
+// launch_commit take one aggregate each (nas_api.hip's launch_cost a CostArgs).
+// A call site builds the base -- fit_args / merge_lists / commit_args there
+// know the context's buffers -- and assigns the fields that differ, by name.
+// precheck() is what a launcher decides before it launches anything: Empty
+// returns hipSuccess, Invalid hipErrorInvalidValue (host code, also run
+// without a GPU: tests/sanitize/launch_args_driver.cpp).
+enum class Pre { Launch, Empty, Invalid };
+inline hipError_t pre_error(Pre p) { return p == Pre::Invalid ? hipErrorInvalidValue : hipSuccess; }
+
+struct FitArgs {
+    const int32_t *cap = nullptr;         // [3][N]
+    int N = 0, n0 = 0, nloc = 0, Mp = 0;  // nodes; this shard's first node, count, padded count
+    const int32_t *req = nullptr;         // [3][Pp]
+    int Pp = 0, p0 = 0, np = 0;           // pods [p0, p0 + np)
+    uint64_t *mask = nullptr;
+    const Dyn *dyn = nullptr;
+    int batch = 1;
+    // rowmap (gathered rescore view, batch 1): view row q is pod rowmap[q] -- its
+    // requests (k_fit, main array with row stride req_stride) and traffic row
+    // (k_cost_topk, main WA) are read in place, no gathered copy
+    const int32_t *rowmap = nullptr;
+    int req_stride = 0;
+    // el (batch 1): the constrained kernels -- pod p's words are el->require[p] /
+    // el->tolerate[p] of the main pod array (a view's row q: pod rowmap[q]); the
+    // words are one cluster's, [N] per node and [Pp] per pod
+    const Elig *el = nullptr;
+};
+inline Pre precheck(const FitArgs &a) {
+    const Elig *el = a.el;
+    if (a.rowmap && a.batch != 1) return Pre::Invalid;
+    if (el && (a.batch != 1 || !el->labels || !el->taints || !el->require || !el->tolerate))
+        return Pre::Invalid;
+    return a.np <= 0 ? Pre::Empty : Pre::Launch;
+}
+hipError_t launch_fit(hipStream_t st, const FitArgs &a);
+
+// source lists keys / bounds [n_lists], `stride` / `bstride` words apart and
+// indexed from pod src_p0; pods [p0, p0 + np) (or the window dyn) merge into
+// cand_key / cand_bound, indexed from pod dst_p0
+struct MergeArgs {
+    const uint64_t *keys = nullptr, *bounds = nullptr;
+    int n_lists = 0;
+    int64_t stride = 0, bstride = 0;
+    uint64_t *cand_key = nullptr, *cand_bound = nullptr;
+    int src_p0 = 0, p0 = 0, np = 0, dst_p0 = 0;
+    const Dyn *dyn = nullptr;
+    int batch = 1;
+    int64_t dst_cluster_pods = 0;      // batch: the clusters' destinations, this many pods apart
+    const int32_t *dst_idx = nullptr;  // (batch 1) row r's lists go to pod dst_idx[r]'s slots
+    // (batch 1, no window) the launch also starts a pass's status words:
+    // init_status[0] = -1 (halt), [1 .. 2*STATUS_INTS) = 0
+    int32_t *init_status = nullptr;
+};
+inline Pre precheck(const MergeArgs &a) {
+    if ((a.dyn ? a.dyn->win : a.np) <= 0) return Pre::Empty;
+    if (a.dst_idx && a.batch != 1) return Pre::Invalid;
+    if (a.init_status && (a.dyn || a.batch != 1)) return Pre::Invalid;
+    return Pre::Launch;
+}
+hipError_t launch_merge(hipStream_t st, const MergeArgs &a);
+
+// the commit keeps the working capacity in LDS (and publishes only final
+// values, at the end of each launch) for clusters of up to this many nodes
+bool commit_in_lds(int N);
+constexpr int COMMIT_STATUS_WORDS = STATUS_INTS + 3;
+struct CommitArgs {
+    const uint64_t *cand_key = nullptr, *cand_bound = nullptr;
+    const int32_t *req = nullptr;
+    int Pp = 0, p_begin = 0, p_end = 0;  // p_begin < 0: the walk resumes from the halt word
+    int32_t *cap = nullptr;
+    int N = 0;
+    int32_t *out_node = nullptr, *out_cost_i = nullptr, *halt = nullptr;
+    const uint8_t *zrow = nullptr;  // zero-traffic pods (launch_zero_rows)
+    int batch = 1;
+    int32_t *pub = nullptr;  // published capacity (the L2 commit's cap_snap)
+    // pinned host rows the walk's placements / raw costs are copied to as it
+    // ends; a batch stages whole clusters, [cluster][p_end] rows from pod 0
+    int32_t *stage_node = nullptr, *stage_cost = nullptr;
+    // stage_status (batch 1): after the walk the commit copies the status words
+    // status[0 .. COMMIT_STATUS_WORDS) there (pinned host memory)
+    int32_t *stage_status = nullptr;
+};
+inline Pre precheck(const CommitArgs &a) {
+    if (a.p_begin >= 0 && a.p_end <= a.p_begin) return Pre::Empty;
+    if (a.stage_node && (a.p_begin < 0 || (a.batch != 1 && a.p_begin != 0))) return Pre::Invalid;
+    if (a.stage_status && a.batch != 1) return Pre::Invalid;
+    return Pre::Launch;
+}
+hipError_t launch_commit(hipStream_t st, const CommitArgs &a);
+
+// nas_api.hip's launch_cost: one cost/top-k launch over the context's operands
+// and partial lists, pods [p0, p0 + np) of rows Pp apart (or a window / view)
+struct CostArgs {
+    int Pp = 0, p0 = 0, np = 0;
+    const Ovf *ovf = nullptr;  // nullptr: the context's lists as they are (make_ovf)
+    const Dyn *dyn = nullptr;
+    int batch = 1;
+    const int32_t *rowmap = nullptr;
+    const FitSrc *fit = nullptr;  // the fused fit (main pod ranges only)
+    bool force_narrow = false;    // 256 x 256 tiles even where the wide tile applies
+    uint32_t *cache = nullptr;
+};
 
 // pods per tile of the wide cost kernel for this (compute) dtype when it is
 // built in (384), else COST_BN
@@ -336,24 +426,6 @@ hipError_t launch_cost_topk(hipStream_t st, int dtype, const void *Lt, const voi
 // cache (main pod ranges only): every (pod, local node) cost of the launch as
 // its orderable 32-bit key into cache[cluster][Pp][Mp] (the cost-row cache,
 // rescored from by launch_rescore_cached)
-hipError_t launch_merge(hipStream_t st, const uint64_t *keys, const uint64_t *bounds, int n_lists,
-                        int64_t stride, int64_t bstride, int src_p0, int p0, int np,
-                        uint64_t *cand_key, uint64_t *cand_bound, int dst_p0 = 0,
-                        const Dyn *dyn = nullptr, int dyn_flags = 0, int batch = 1,
-                        int64_t dst_cluster_pods = 0, const int32_t *dst_idx = nullptr,
-                        int32_t *init_status = nullptr);
-// the commit keeps the working capacity in LDS (and publishes only final
-// values, at the end of each launch) for clusters of up to this many nodes
-bool commit_in_lds(int N);
-hipError_t launch_commit(hipStream_t st, const uint64_t *cand_key, const uint64_t *cand_bound,
-                         const int32_t *req, int Pp, int p_begin, int p_end, int32_t *cap, int N,
-                         int32_t *out_node, int32_t *out_cost_i, int32_t *halt, int batch = 1,
-                         int32_t *pub = nullptr, const uint8_t *zrow = nullptr,
-                         int32_t *stage_node = nullptr, int32_t *stage_cost = nullptr,
-                         int32_t *stage_status = nullptr);
-// stage_status (batch 1): after the walk the commit copies the status words
-// status[0 .. COMMIT_STATUS_WORDS) there (pinned host memory)
-constexpr int COMMIT_STATUS_WORDS = STATUS_INTS + 3;
 // zrow[r] = 1 iff traffic row r (row_bytes bytes of WA) is all zero bytes and
 // has no overflow entries (ovf_ptr may be null): the pod's every cost is 0
 hipError_t launch_zero_rows(hipStream_t st, const void *WA, int64_t rows, int64_t row_bytes,

@@ -1083,6 +1083,7 @@ k_cost_topk(const unsigned char *__restrict__ Lt, const unsigned char *__restric
 // does the bound: every intermediate kept[7] is >= the final kept[7], so the
 // result is min(all list bounds, final kept[7]) -- identical to a serial fold.
 constexpr int MERGE_LANES = 8;
+constexpr int MERGE_SRC_WINDOW = 1, MERGE_DST_WINDOW = 2;  // dyn_flags (k_cost.hip)
 // 64 pods per workgroup (2 waves per SIMD at 56 VGPRs): still co-resides
 // with a 256 x 256 cost workgroup (2 waves per SIMD at 192 VGPRs) on a node
 // shard; 1,024-thread blocks do not, and measured 7% slower at G = 8 (the

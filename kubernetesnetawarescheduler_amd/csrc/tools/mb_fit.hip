@@ -125,9 +125,17 @@ int main(int argc, char **argv) {
     const double bytes = (double)P * n_chunks * 8 + 12.0 * (N + P);
     // the product kernel
     std::vector<float> t(reps);
+    FitArgs fa;
+    fa.cap = dcap;
+    fa.N = fa.nloc = N;
+    fa.Mp = Mp;
+    fa.req = dreq;
+    fa.Pp = Pp;
+    fa.np = P;
+    fa.mask = (uint64_t *)m0;
     for (int r = 0; r < reps; ++r) {
         CK(hipEventRecord(a));
-        CK(launch_fit(0, dcap, N, 0, N, Mp, dreq, P, Pp, 0, P, (uint64_t *)m0));
+        CK(launch_fit(0, fa));
         CK(hipEventRecord(b));
         CK(hipEventSynchronize(b));
         CK(hipEventElapsedTime(&t[r], a, b));

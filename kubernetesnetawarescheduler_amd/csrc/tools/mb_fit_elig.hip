@@ -87,12 +87,20 @@ int main(int argc, char **argv) {
     CK(hipEventCreate(&a));
     CK(hipEventCreate(&b));
     std::vector<float> t[4];  // 0: unconstrained, 1..3: the patterns
+    FitArgs fa;
+    fa.cap = dcap;
+    fa.N = fa.nloc = N;
+    fa.Mp = Mp;
+    fa.req = dreq;
+    fa.Pp = Pp;
+    fa.np = P;
+    fa.mask = (uint64_t *)mask;
     for (int r = -3; r < rounds; ++r)  // (three warm-up rounds)
         for (int v = 0; v < 4; ++v) {
             float ms = 0;
+            fa.el = v ? &el[v - 1] : nullptr;
             CK(hipEventRecord(a));
-            CK(launch_fit(0, dcap, N, 0, N, Mp, dreq, P, Pp, 0, P, (uint64_t *)mask, nullptr, 1,
-                          nullptr, 0, v ? &el[v - 1] : nullptr));
+            CK(launch_fit(0, fa));
             CK(hipEventRecord(b));
             CK(hipEventSynchronize(b));
             CK(hipEventElapsedTime(&ms, a, b));
@@ -108,8 +116,8 @@ int main(int argc, char **argv) {
     // every 97th pod's words of every pattern against the rule on the host
     std::vector<u64w> h((size_t)n_chunks * Pp);
     for (int k = 0; k < 3; ++k) {
-        CK(launch_fit(0, dcap, N, 0, N, Mp, dreq, P, Pp, 0, P, (uint64_t *)mask, nullptr, 1, nullptr,
-                      0, &el[k]));
+        fa.el = &el[k];
+        CK(launch_fit(0, fa));
         CK(hipMemcpy(h.data(), mask, h.size() * 8, hipMemcpyDeviceToHost));
         size_t bad = 0, set = 0;
         for (int p = 0; p < P; p += 97)

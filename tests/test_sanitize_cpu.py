@@ -61,3 +61,28 @@ def test_asan_ubsan_host_and_oracle(tmp_path):
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert "SAN OK" in r.stdout
     assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr
+
+
+CSRC = os.path.join(ROOT, "kubernetesnetawarescheduler_amd", "csrc")
+HIP_INCLUDE = "/opt/rocm/include"
+
+
+@pytest.mark.skipif(shutil.which("g++") is None or not os.path.isdir(HIP_INCLUDE),
+                    reason="needs g++ and the HIP headers")
+def test_asan_ubsan_launch_args(tmp_path):
+    """The host side of the kernel launch boundary (csrc/nas_internal.h: the
+    argument structs of launch_fit / launch_merge / launch_commit and their
+    precheck()) in a stand-alone program: the structs' defaults, and every
+    early return and hipErrorInvalidValue condition against the rules as the
+    launchers stated them on positional parameters.  The checks precede any
+    launch, so the program needs neither a GPU nor the HIP runtime."""
+    exe = tmp_path / "launch_args_driver"
+    subprocess.run(["g++", "-std=c++17", *SAN, "-D__HIP_PLATFORM_AMD__", "-I", HIP_INCLUDE,
+                    "-I", CSRC, os.path.join(ROOT, "tests", "sanitize", "launch_args_driver.cpp"),
+                    "-o", str(exe)], check=True)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:halt_on_error=1",
+               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
+    r = subprocess.run([str(exe)], env=env, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert "LAUNCH ARGS OK" in r.stdout
+    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr
