@@ -362,6 +362,42 @@ int nas_upload_traffic_csr(nas_ctx *ctx, const int32_t *row_ptr, const int32_t *
  * bit j of mask_out[c * P + p] == pod p fits node 64c + j. */
 int nas_filter(nas_ctx *ctx, uint64_t *mask_out);
 
+/* ---- why a pod does not fit: per-reason node counts -------------------------
+ * One record of NAS_WHY_COUNT int32 per listed pod, counted over ALL n nodes
+ * against the working capacity at the time of the call (one kernel,
+ * k_explain.hip).  A node is owned by the first filter that rejects it, in
+ * Kubernetes' filter-plugin order; the resource filter reports every short
+ * resource:
+ *   - a node with a taint the pod does not tolerate counts under TAINT only;
+ *   - otherwise a node lacking a required label counts under SELECTOR only;
+ *   - otherwise a node where a request exceeds the free amount (req > free, the
+ *     fit kernels' comparison: equality fits) counts once under RESOURCES and
+ *     under each of CPU / MEM / PODS that is short;
+ *   - otherwise it counts under FIT.
+ * Hence TAINT + SELECTOR + RESOURCES + FIT == NODES for every pod.  The
+ * eligibility words are those of nas_upload_*_constraints (a side never
+ * uploaded is all zero); with no constraints uploaded TAINT = SELECTOR = 0.
+ * After nas_place a pod that got NAS_EMPTY has FIT == 0 (capacity only shrinks
+ * within a pass); placed pods carry no such promise.
+ * pods: n_pods indices into the uploaded pods, in any order, duplicates
+ * allowed; NULL = pods 0 .. n_pods-1.  An index outside [0, P) or n_pods < 0
+ * is NAS_ERR_ARG; n_pods == 0 is NAS_OK.  Missing capacity / pods / geometry
+ * is NAS_ERR_STATE (as nas_filter), constraint words of another shape
+ * NAS_ERR_ARG, a cluster batch NAS_ERR_UNSUPPORTED.  On a node shard the
+ * counts still cover all n nodes (capacity and node words are replicated) and
+ * no collective is issued.  Blocking; nas_timings is not touched. */
+#define NAS_WHY_TAINT     0  /* nodes with a taint the pod does not tolerate */
+#define NAS_WHY_SELECTOR  1  /* of the rest: nodes lacking a required label */
+#define NAS_WHY_RESOURCES 2  /* of the eligible rest: nodes where >= 1 resource is short */
+#define NAS_WHY_CPU       3  /*   of those, req_cpu  > free_cpu  (a node may count in */
+#define NAS_WHY_MEM       4  /*   of those, req_mem  > free_mem   several of 3..5)    */
+#define NAS_WHY_PODS      5  /*   of those, req_pods > free_pods                      */
+#define NAS_WHY_FIT       6  /* nodes the pod fits now */
+#define NAS_WHY_NODES     7  /* n */
+#define NAS_WHY_COUNT     8
+int nas_explain(nas_ctx *ctx, const int32_t *pods, int32_t n_pods,
+                int32_t *counts_out /* [n_pods * NAS_WHY_COUNT] */);
+
 /* Place all uploaded pods: fit, cost = WA x L on MFMA with the top-k fused
  * in the epilogue, then greedy commit in pod order with capacity update.
  * node_out[P]: chosen node or NAS_EMPTY.  cost_out[P] (optional): the

@@ -200,6 +200,22 @@ int nas_host_set_pod_constraints(nas_host_sched *s, const char *ns_name,
 int nas_host_intern_bits(const char *const *universe, int32_t n_universe, const char *const *have,
                          int32_t n_have, uint64_t *bits_out);
 
+/* ---- why a pod is unschedulable (nas.h: nas_explain) ------------------------
+ * The FailedScheduling line of one nas_explain record, pure (no scheduler, no
+ * GPU): "{FIT}/{NODES} nodes are available", then for each non-zero count, in
+ * this order, "{n} node(s) had untolerated taint", "{n} node(s) didn't match
+ * Pod's node selector", "{n} Insufficient cpu", "{n} Insufficient memory",
+ * "{n} Too many pods" -- joined as head + ": " + parts separated by ", " +
+ * ".", or head + "." without parts.  NAS_ERR_ARG for a NULL argument or a cap
+ * too small for the whole string and its NUL (buf is then left untouched:
+ * never a truncated text). */
+int nas_host_explain_message(const int32_t counts[8], char *buf, size_t cap);
+/* on != 0: nas_host_place_pending makes one nas_explain call, after
+ * nas_place, for the pods that came back unplaced and reports each as
+ * NAS_HOST_UNSCHEDULABLE with that message (counts against the capacity the
+ * pass left, so FIT is 0).  Default 0: the two fixed messages above. */
+int nas_host_set_explain(nas_host_sched *s, int32_t on);
+
 #ifdef __cplusplus
 }
 #endif

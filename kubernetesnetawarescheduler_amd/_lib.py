@@ -40,6 +40,16 @@ NAS_DBG_MASKED_STREAMS_IDLE = 2
 NAS_DBG_LIVE_CONTEXTS = 3
 NAS_DBG_COUNT = 4
 K_CANDIDATES = 8
+# slots of one pod's nas_explain record (include/nas.h)
+NAS_WHY_TAINT = 0
+NAS_WHY_SELECTOR = 1
+NAS_WHY_RESOURCES = 2
+NAS_WHY_CPU = 3
+NAS_WHY_MEM = 4
+NAS_WHY_PODS = 5
+NAS_WHY_FIT = 6
+NAS_WHY_NODES = 7
+NAS_WHY_COUNT = 8
 VOTE_NOPOS = 0x7FFFFFFF
 # include/nas.h nas_vote_partial: six (value, pos1, reserved) extrema, NAS_VP_* order
 VOTE_FIELDS = ("cpu", "mem", "bw", "rx", "tx", "disk")
@@ -106,6 +116,7 @@ SIGNATURES = {
     "nas_upload_traffic_dense": (_I, [_CTX, _V, _I, _I, _I]),
     "nas_upload_traffic_csr": (_I, [_CTX, _V, _V, _V, _I, _I, _I, _c.c_int64]),
     "nas_filter": (_I, [_CTX, _V]),
+    "nas_explain": (_I, [_CTX, _V, _I, _V]),
     "nas_score": (_I, [_CTX]),
     "nas_place": (_I, [_CTX, _V, _V, _V]),
     "nas_get_candidates": (_I, [_CTX, _V, _V, _V, _V, _V]),

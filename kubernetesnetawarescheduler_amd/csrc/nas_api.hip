@@ -1677,7 +1677,7 @@ void nas_destroy(nas_ctx *ctx) {
                       &ctx->gather[0], &ctx->gather[1], &ctx->gather[2], &ctx->xsend[2],
                       &ctx->out_node, &ctx->out_cost_f, &ctx->out_cost_i,
                       &ctx->g_words, &ctx->g_idx, &ctx->g_key,
-                      &ctx->g_bound, &ctx->g_gk, &ctx->g_gb, &ctx->status, &ctx->scratch,
+                      &ctx->g_bound, &ctx->g_gk, &ctx->g_gb, &ctx->status, &ctx->scratch, &ctx->explain,
                       &ctx->vote_part, &ctx->vote_gather, &ctx->xsend[0], &ctx->xsend[1],
                       &ctx->ovf_ptr, &ctx->ovf_m, &ctx->ovf_e, &ctx->Lr, &ctx->Lt6, &ctx->WA6,
                       &ctx->commit_flag, &ctx->zrow, &ctx->cost_cache, &ctx->node_con,
@@ -2457,6 +2457,47 @@ int nas_filter(nas_ctx *ctx, uint64_t *mask_out) {
     HIPCK(hipStreamSynchronize(ctx->stream));
     tm.span(T_FIT, a, b);
     ctx->timings.fit_ms = tm.total(T_FIT);
+    return NAS_OK;
+}
+
+int nas_explain(nas_ctx *ctx, const int32_t *pods, int32_t n_pods, int32_t *counts_out) {
+    NAS_RANGE("nas_explain");
+    OK(bind(ctx));
+    OK(no_batch(ctx, "nas_explain"));
+    if (!ctx->have_cap || !ctx->have_pods || ctx->N <= 0)
+        return nas::fail(ctx, NAS_ERR_STATE, "nas_explain needs capacity and pods");
+    if (ctx->cap_n != ctx->N || ctx->req_P != ctx->P)
+        return nas::fail(ctx, NAS_ERR_STATE, "nas_explain: capacity/pods do not match the geometry");
+    if (n_pods < 0 || (n_pods > 0 && !counts_out))
+        return nas::fail(ctx, NAS_ERR_ARG, "nas_explain: n_pods / counts_out");
+    if (!pods && n_pods > ctx->P)
+        return nas::fail(ctx, NAS_ERR_ARG,
+                         "nas_explain: " + std::to_string(n_pods) + " pods asked for, " +
+                             std::to_string(ctx->P) + " are uploaded");
+    if (pods)
+        for (int32_t i = 0; i < n_pods; ++i)
+            if (pods[i] < 0 || pods[i] >= ctx->P)
+                return nas::fail(ctx, NAS_ERR_ARG,
+                                 "nas_explain: pods[" + std::to_string(i) + "] = " +
+                                     std::to_string(pods[i]) + " is not an uploaded pod");
+    OK(check_constraints(ctx, ctx->N, ctx->P));
+    if (n_pods == 0) return NAS_OK;
+    OK(alloc_extended(ctx));
+    OK(prepare_constraints(ctx));
+    // the records, then the list; all N nodes whatever this rank's shard (the
+    // capacity and the node words are replicated at full length)
+    const size_t rec_bytes = (size_t)n_pods * NAS_WHY_COUNT * 4;
+    OK(nas::ensure(ctx, ctx->explain, rec_bytes + (pods ? (size_t)n_pods * 4 : 0)));
+    int32_t *rec = ctx->explain.as<int32_t>(), *list = nullptr;
+    if (pods) {
+        list = rec + (size_t)n_pods * NAS_WHY_COUNT;
+        HIPCK(hipMemcpyAsync(list, pods, (size_t)n_pods * 4, hipMemcpyHostToDevice, ctx->stream));
+    }
+    HIPCK(hipMemsetAsync(rec, 0, rec_bytes, ctx->stream));
+    HIPCK(nas::launch_explain(ctx->stream, ctx->cap.as<int32_t>(), ctx->N, ctx->req.as<int32_t>(),
+                              ctx->Pp, list, n_pods, rec, elig(ctx), ctx->n_cu));
+    HIPCK(hipMemcpyAsync(counts_out, rec, rec_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCK(hipStreamSynchronize(ctx->stream));
     return NAS_OK;
 }
 

@@ -191,6 +191,7 @@ struct nas_ctx {
     nas::DevBuf host_status; // pinned
     nas::DevBuf ref_stage;   // pinned: nas_score_reference results [P] best | [P][6] winners
     nas::DevBuf scratch;
+    nas::DevBuf explain;     // nas_explain: [n] records of NAS_WHY_COUNT ints | [n] listed pods
     // exact int32 traffic (nas::Ovf): entries outside the int8 plane, and Lr
     nas::DevBuf ovf_ptr, ovf_m, ovf_e, Lr;
     int64_t ovf_n = 0;          // entries (0: the plane is the traffic)
@@ -346,6 +347,14 @@ inline Pre precheck(const FitArgs &a) {
     return a.np <= 0 ? Pre::Empty : Pre::Launch;
 }
 hipError_t launch_fit(hipStream_t st, const FitArgs &a);
+
+// k_explain.hip (nas_explain): out[i][NAS_WHY_*] += list entry i's per-reason
+// node counts over all N nodes of cap ([3][N], global node index) -- `out`
+// ([n_pods][NAS_WHY_COUNT]) zeroed by the caller.  Entry i is pod pods[i]
+// (nullptr: pod i) of req ([3][rs]) and, with el, of its pod words; n_cu sizes
+// the grid
+hipError_t launch_explain(hipStream_t st, const int32_t *cap, int N, const int32_t *req, int rs,
+                          const int32_t *pods, int n_pods, int32_t *out, const Elig *el, int n_cu);
 
 // source lists keys / bounds [n_lists], `stride` / `bstride` words apart and
 // indexed from pod src_p0; pods [p0, p0 + np) (or the window dyn) merge into

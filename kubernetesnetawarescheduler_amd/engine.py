@@ -402,6 +402,20 @@ class Engine:
         self._ck(self._L.nas_filter(self._h, ptr(mask)))
         return mask
 
+    def explain(self, pods=None):
+        """nas_explain: per-reason node counts, an int32 array (n, 8) with the
+        columns _lib.NAS_WHY_* (taint, selector, resources, cpu, mem, pods,
+        fit, nodes), against the working capacity now.  pods: indices into the
+        uploaded pods (any order, duplicates allowed); None: all of them."""
+        if pods is None:
+            idx, n = None, self.n_pods
+        else:
+            idx = as_c(pods, np.int32).reshape(-1)
+            n = idx.shape[0]
+        out = np.zeros((n, _lib.NAS_WHY_COUNT), np.int32)
+        self._ck(self._L.nas_explain(self._h, ptr(idx), n, ptr(out)))
+        return out
+
     def score(self):
         self._ck(self._L.nas_score(self._h))
 

@@ -405,6 +405,24 @@ int nas_host_intern_bits(const char *const *universe, int32_t n_universe, const 
     return NAS_OK;
 }
 
+int nas_host_explain_message(const int32_t counts[8], char *buf, size_t cap) {
+    if (!counts || !buf) return NAS_ERR_ARG;
+    try {
+        const std::string msg = explain_message(counts);
+        if (msg.size() + 1 > cap) return NAS_ERR_ARG;  // never a truncated text
+        std::memcpy(buf, msg.c_str(), msg.size() + 1);
+    } catch (...) {
+        return NAS_ERR_STATE;
+    }
+    return NAS_OK;
+}
+
+int nas_host_set_explain(nas_host_sched *s, int32_t on) {
+    if (!s) return NAS_ERR_ARG;
+    s->s->set_explain(on != 0);
+    return NAS_OK;
+}
+
 int nas_host_place_pending(nas_host_sched *s, nas_host_outcome *out, int32_t *n_out) {
     if (!s || !out || !n_out) return NAS_ERR_ARG;
     GUARD(s, {

@@ -38,6 +38,26 @@ uint64_t intern_bits(const std::vector<std::string> &universe, const std::vector
     return bits;
 }
 
+std::string explain_message(const int32_t counts[NAS_WHY_COUNT]) {
+    static const struct {
+        int slot;
+        const char *text;
+    } kParts[] = {{NAS_WHY_TAINT, " node(s) had untolerated taint"},
+                  {NAS_WHY_SELECTOR, " node(s) didn't match Pod's node selector"},
+                  {NAS_WHY_CPU, " Insufficient cpu"},
+                  {NAS_WHY_MEM, " Insufficient memory"},
+                  {NAS_WHY_PODS, " Too many pods"}};
+    std::string msg = std::to_string(counts[NAS_WHY_FIT]) + "/" +
+                      std::to_string(counts[NAS_WHY_NODES]) + " nodes are available";
+    const char *sep = ": ";
+    for (const auto &p : kParts) {
+        if (counts[p.slot] == 0) continue;
+        msg += sep + std::to_string(counts[p.slot]) + p.text;
+        sep = ", ";
+    }
+    return msg + ".";
+}
+
 CustomScheduler::CustomScheduler(nas_ctx *ctx, ClusterApi &api, MetricsSource &src, MapOrder &order)
     : ctx_(ctx), api_(api), src_(src), order_(order), topo_(reference_topology()) {}
 
@@ -310,7 +330,24 @@ std::vector<std::pair<Pod, Outcome>> CustomScheduler::place_pending() {
     }
     std::vector<int32_t> node_out(P);
     check(ctx_, nas_place(ctx_, node_out.data(), nullptr, nullptr), "nas_place");
+    // set_explain: one nas_explain call for the pods that came back unplaced,
+    // against the capacity the pass left
+    std::vector<int32_t> unplaced, why;
+    if (explain_)
+        for (int p = 0; p < P; ++p)
+            if (node_out[p] < 0) unplaced.push_back(p);
+    if (!unplaced.empty()) {
+        why.resize(unplaced.size() * NAS_WHY_COUNT);
+        check(ctx_, nas_explain(ctx_, unplaced.data(), (int32_t)unplaced.size(), why.data()),
+              "nas_explain");
+    }
+    size_t n_why = 0;
     for (int p = 0; p < P; ++p) {
+        if (node_out[p] < 0 && explain_) {
+            out.push_back({pods[p], {Outcome::UNSCHEDULABLE, "",
+                                     explain_message(why.data() + n_why++ * NAS_WHY_COUNT)}});
+            continue;
+        }
         if (node_out[p] < 0) {
             bool any = false;  // some node is eligible: the requests did not fit
             for (int i = 0; i < n && !any; ++i)

@@ -90,6 +90,11 @@ std::vector<Endpoint> reference_topology();  // :275-279
 // ignored); throws std::invalid_argument for more than 64 universe strings
 uint64_t intern_bits(const std::vector<std::string> &universe, const std::vector<std::string> &have);
 
+// the FailedScheduling line of one nas_explain record (counts[NAS_WHY_COUNT]):
+// "{FIT}/{NODES} nodes are available", then ": " and the non-zero counts of
+// taint, selector, cpu, memory, pods in that order, joined by ", "; then "."
+std::string explain_message(const int32_t *counts);
+
 struct Outcome {
     enum Kind { BOUND, NO_POD, LIST_ERROR, BIND_ERROR, EVENT_ERROR, PANIC, UNSCHEDULABLE } kind;
     std::string node, message;
@@ -137,6 +142,11 @@ public:
         pod_con_[ns_name] = {std::move(selector), std::move(tolerations)};
     }
 
+    // place_pending's message for an unschedulable pod: off (default) one of
+    // the two fixed strings; on, explain_message of the pod's nas_explain
+    // record, from one nas_explain call behind nas_place
+    void set_explain(bool on) { explain_ = on; }
+
     void set_topology(std::vector<Endpoint> t) { topo_ = std::move(t); }
     // replaces the reference's node -> report map (:505-510) entry by entry
     void add_iperf_path(const std::string &node, const std::string &path) {
@@ -171,6 +181,7 @@ private:
     // first: labels / node selector, second: taints / tolerations
     using StringSets = std::pair<std::vector<std::string>, std::vector<std::string>>;
     std::map<std::string, StringSets> node_con_, pod_con_;
+    bool explain_ = false;
 };
 
 }  // namespace nas_host

@@ -91,6 +91,8 @@ SIGNATURES = {
                                                 _c.POINTER(_CS), _c.c_int32]),
     "nas_host_intern_bits": (_c.c_int, [_c.POINTER(_CS), _c.c_int32, _c.POINTER(_CS), _c.c_int32,
                                         _c.POINTER(_c.c_uint64)]),
+    "nas_host_explain_message": (_c.c_int, [_I32P, _c.c_char_p, _c.c_size_t]),
+    "nas_host_set_explain": (_c.c_int, [_P, _c.c_int32]),
 }
 
 _HL = None
@@ -208,6 +210,20 @@ def intern_bits(universe, have):
     if rc != 0:
         raise NasError(rc, f"nas_host_intern_bits: a universe of {nu} strings")
     return bits.value
+
+
+def explain_message(counts, cap=256):
+    """The FailedScheduling line of one Engine.explain record (8 counts, the
+    _lib.NAS_WHY_* slots): nas_host_explain_message.  Raises NasError when the
+    text and its NUL do not fit `cap` bytes."""
+    c = np.ascontiguousarray(counts, np.int32).reshape(-1)
+    if c.shape[0] != 8:
+        raise ValueError("explain_message takes one record of 8 counts")
+    buf = _c.create_string_buffer(max(1, cap))
+    rc = hostlib().nas_host_explain_message(c.ctypes.data_as(_I32P), buf, cap)
+    if rc != 0:
+        raise NasError(rc, f"nas_host_explain_message: the text does not fit {cap} bytes")
+    return buf.value.decode()
 
 
 class GoPanicError(RuntimeError):
@@ -356,6 +372,12 @@ class HostScheduler:
         l, nl = _strs(node_selector)
         t, nt = _strs(tolerations)
         self._ck(self._L.nas_host_set_pod_constraints(self._h, _b(ns_name), l, nl, t, nt))
+
+    def set_explain(self, on):
+        """place_pending reports each unschedulable pod with the message of its
+        nas_explain record (one GPU call per pass) instead of the two fixed
+        strings; off by default."""
+        self._ck(self._L.nas_host_set_explain(self._h, 1 if on else 0))
 
     def enqueue(self, ns, name, uid="", scheduler_name="netAwareScheduler", node_name="",
                 cpu_milli=0, mem_kib=0, peers=()):

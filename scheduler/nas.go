@@ -246,6 +246,28 @@ func (e *nasEngine) clearConstraints() error {
 	return nasErr(e.ctx, C.nas_clear_constraints(e.ctx), "nas_clear_constraints")
 }
 
+// Explain says why pods do not fit: one record per listed pod (indices into
+// the pods of the last placeBatch, any order, duplicates allowed) of node
+// counts by reason -- the slots C.NAS_WHY_TAINT ... C.NAS_WHY_NODES of
+// include/nas.h -- against the capacity the pass left.  A node counts under the
+// first filter that rejects it (taint, then selector, then resources, there
+// under every short resource), so taint + selector + resources + fit == nodes.
+// Call it after placeBatch for the pods that came back "": their fit count is
+// 0 and the record is the FailedScheduling event's text (INTEGRATION.md).
+func (e *nasEngine) Explain(pods []int32) ([][8]int32, error) {
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	if len(pods) == 0 {
+		return nil, nil
+	}
+	out := make([][C.NAS_WHY_COUNT]int32, len(pods))
+	rc := C.nas_explain(e.ctx, (*C.int32_t)(&pods[0]), C.int32_t(len(pods)), (*C.int32_t)(&out[0][0]))
+	if err := nasErr(e.ctx, rc, "nas_explain"); err != nil {
+		return nil, err
+	}
+	return out, nil
+}
+
 // placeBatch is the network-aware path: pods drained from podQueue (:129) in
 // arrival order, each with its requests and its traffic (MB, fp32) to
 // already-bound peers as CSR -- peerNode[rowPtr[p]:rowPtr[p+1]] is the node
