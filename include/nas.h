@@ -398,6 +398,80 @@ int nas_filter(nas_ctx *ctx, uint64_t *mask_out);
 int nas_explain(nas_ctx *ctx, const int32_t *pods, int32_t n_pods,
                 int32_t *counts_out /* [n_pods * NAS_WHY_COUNT] */);
 
+/* ---- preemption: a node and the lower-priority pods to evict there ----------
+ * The step after "0/n nodes are available": may the pod evict lower-priority
+ * pods somewhere, and if so where and which ones (kube-scheduler's
+ * pickOneNodeForPreemption without PodDisruptionBudgets and start times).
+ *
+ * The running ("bound") pods: bound pod b runs on node[b] with priority[b]
+ * (any int32) and holds the three requests (each >= 0).  B == 0 (NULL arrays
+ * allowed) clears the table.  Capacity must have been uploaded first (it fixes
+ * n); otherwise NAS_ERR_STATE.  node[b] outside [0, n), a negative request or
+ * B < 0 is NAS_ERR_ARG (the message names the first bad entry); a node whose
+ * bound requests sum above INT32_MAX in some resource, or a cluster batch, is
+ * NAS_ERR_UNSUPPORTED.  The free capacity is the working capacity, as
+ * everywhere else: bound requests are what eviction gives back on top of it,
+ * and no consistency between the two is required.  The library builds the
+ * per-node index on the host -- a stable order by (node ascending, priority
+ * descending, b ascending) plus row offsets -- and the table persists until it
+ * is uploaded again.  If capacity is later uploaded with another n,
+ * nas_preempt returns NAS_ERR_ARG until the table is uploaded again.  On a
+ * node shard every rank uploads the full table, as it does capacity. */
+int nas_upload_bound(nas_ctx *ctx, const int32_t *node, const int32_t *priority,
+                     const int32_t *req_cpu_milli, const int32_t *req_mem_kib,
+                     const int32_t *req_pods, int32_t B);
+
+/* The query.  pods as in nas_explain: n_pods indices into the uploaded pods,
+ * any order, duplicates allowed, NULL = pods 0 .. n_pods-1; priority[i] is the
+ * priority of list entry i and is required.  Every entry is answered on its
+ * own against the working capacity and the bound table at the time of the
+ * call: a what-if per pod, not a sequence (the host applies one answer at a
+ * time and asks again).
+ *
+ * For list entry i (pod p, requests r, priority pi) and node n with free
+ * capacity f:
+ *  1. If constraints are uploaded and n is not eligible for p (untolerated
+ *     taint or missing label), n is not a candidate: evictions cannot fix that.
+ *  2. `lower` is the bound pods on n with priority < pi.  Equal priority is not
+ *     a victim.
+ *  3. avail = f + sum of lower's requests, in 64 bits.  If r > avail in any
+ *     resource, n is not a candidate.
+ *  4. Reprieve: walk `lower` in index order (priority descending, then b
+ *     ascending).  If avail - req_b >= r holds in all three resources, then
+ *     avail -= req_b and b stays; otherwise b is a victim.  Equality fits, as
+ *     in the fit kernels.
+ *  5. The node's key is the tuple (top_priority, priority_sum, n_victims, n),
+ *     and a node without victims sorts before every node with victims.  The
+ *     chosen node is the lexicographic minimum: lowest highest-victim priority,
+ *     then smallest priority sum, then fewest victims, then lowest node index.
+ *     (The "fewest victims" level decides only among victims of priority
+ *     INT32_MIN: otherwise an equal sum at an equal top priority already
+ *     implies an equal count.  It is kept for fidelity with kube-scheduler.)
+ *  6. `candidates` counts the nodes that passed step 3.
+ *
+ * victims_out[i * max_victims + j] holds the chosen node's victims as original
+ * bound indices b, in walk order: the first min(n_victims, max_victims)
+ * entries are written, the rest are -1.  victims_out may be NULL with
+ * max_victims == 0.
+ *
+ * Errors mirror nas_explain: a bad index, n_pods < 0, max_victims < 0, or NULL
+ * out / priority (or NULL victims_out with max_victims > 0) with n_pods > 0 is
+ * NAS_ERR_ARG; n_pods == 0 is NAS_OK and nothing is written; no capacity or
+ * pods uploaded is NAS_ERR_STATE; a cluster batch NAS_ERR_UNSUPPORTED;
+ * constraint words of another shape NAS_ERR_ARG.  With no bound table every
+ * node's list is empty: the answer is the lowest fitting node or NAS_EMPTY.
+ * Blocking; nas_timings is not touched.  On a node shard the call covers all n
+ * nodes and issues no collective.  After any error the context stays usable. */
+typedef struct nas_preemption {
+    int32_t node;          /* chosen node, or NAS_EMPTY: no node works even after evictions */
+    int32_t n_victims;     /* 0: the pod fits `node` as it is */
+    int32_t top_priority;  /* highest victim priority; 0 when n_victims == 0 */
+    int32_t candidates;    /* nodes on which the pod fits as is or after evictions */
+    int64_t priority_sum;  /* sum over victims of (priority + 2^31); 0 without victims */
+} nas_preemption;          /* 24 bytes */
+int nas_preempt(nas_ctx *ctx, const int32_t *pods, const int32_t *priority, int32_t n_pods,
+                nas_preemption *out, int32_t *victims_out, int32_t max_victims);
+
 /* Place all uploaded pods: fit, cost = WA x L on MFMA with the top-k fused
  * in the epilogue, then greedy commit in pod order with capacity update.
  * node_out[P]: chosen node or NAS_EMPTY.  cost_out[P] (optional): the

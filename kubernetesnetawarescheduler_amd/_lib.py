@@ -84,6 +84,16 @@ class NasTimings(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class NasPreemption(ctypes.Structure):
+    """include/nas.h nas_preemption: one list entry's answer of nas_preempt."""
+    _fields_ = [("node", ctypes.c_int32), ("n_victims", ctypes.c_int32),
+                ("top_priority", ctypes.c_int32), ("candidates", ctypes.c_int32),
+                ("priority_sum", ctypes.c_int64)]
+
+
+# the same record as a numpy structured dtype (Engine.preempt)
+PREEMPTION_DTYPE = np.dtype([(k, np.dtype(t)) for k, t in NasPreemption._fields_])
+
 _c = ctypes
 _V = _c.c_void_p
 _I = _c.c_int32
@@ -117,6 +127,8 @@ SIGNATURES = {
     "nas_upload_traffic_csr": (_I, [_CTX, _V, _V, _V, _I, _I, _I, _c.c_int64]),
     "nas_filter": (_I, [_CTX, _V]),
     "nas_explain": (_I, [_CTX, _V, _I, _V]),
+    "nas_upload_bound": (_I, [_CTX, _V, _V, _V, _V, _V, _I]),
+    "nas_preempt": (_I, [_CTX, _V, _V, _I, _V, _V, _I]),
     "nas_score": (_I, [_CTX]),
     "nas_place": (_I, [_CTX, _V, _V, _V]),
     "nas_get_candidates": (_I, [_CTX, _V, _V, _V, _V, _V]),

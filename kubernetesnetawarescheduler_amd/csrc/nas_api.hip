@@ -19,6 +19,7 @@
 #include <thread>
 #include <vector>
 
+#include "bound_index.h"
 #include "nas_internal.h"
 
 using nas::DevBuf;
@@ -1681,7 +1682,7 @@ void nas_destroy(nas_ctx *ctx) {
                       &ctx->vote_part, &ctx->vote_gather, &ctx->xsend[0], &ctx->xsend[1],
                       &ctx->ovf_ptr, &ctx->ovf_m, &ctx->ovf_e, &ctx->Lr, &ctx->Lt6, &ctx->WA6,
                       &ctx->commit_flag, &ctx->zrow, &ctx->cost_cache, &ctx->node_con,
-                      &ctx->pod_con};
+                      &ctx->pod_con, &ctx->bound, &ctx->preempt};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     if (ctx->host_status.p) (void)hipHostFree(ctx->host_status.p);
@@ -2497,6 +2498,125 @@ int nas_explain(nas_ctx *ctx, const int32_t *pods, int32_t n_pods, int32_t *coun
     HIPCK(nas::launch_explain(ctx->stream, ctx->cap.as<int32_t>(), ctx->N, ctx->req.as<int32_t>(),
                               ctx->Pp, list, n_pods, rec, elig(ctx), ctx->n_cu));
     HIPCK(hipMemcpyAsync(counts_out, rec, rec_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCK(hipStreamSynchronize(ctx->stream));
+    return NAS_OK;
+}
+
+// ---- preemption (k_preempt.hip): the bound pods' index and the query
+namespace {
+// ctx->bound = row [n + 1] (padded to whole 16 bytes) | tab [BT_ROWS][B]
+size_t bound_row_ints(int32_t n) { return (size_t)nas::round_up((int64_t)n + 1, 4); }
+}  // namespace
+
+int nas_upload_bound(nas_ctx *ctx, const int32_t *node, const int32_t *priority,
+                     const int32_t *req_cpu_milli, const int32_t *req_mem_kib,
+                     const int32_t *req_pods, int32_t B) {
+    NAS_RANGE("nas_upload_bound");
+    OK(bind(ctx));
+    OK(no_batch(ctx, "nas_upload_bound"));
+    if (!ctx->have_cap)
+        return nas::fail(ctx, NAS_ERR_STATE, "nas_upload_bound needs capacity (it fixes n)");
+    const int32_t n = ctx->cap_n;
+    nas::BoundIndex ix;
+    std::string msg;
+    const int rc = nas::build_bound_index(node, priority, req_cpu_milli, req_mem_kib, req_pods, B, n,
+                                          ix, msg);
+    if (rc != NAS_OK) return nas::fail(ctx, rc, msg);  // (the table in place stays)
+    ctx->bound_B = 0;  // B == 0: nas_preempt makes the empty rows
+    ctx->bound_n = 0;
+    if (B == 0) return NAS_OK;
+    const size_t rows = bound_row_ints(n);
+    OK(nas::ensure(ctx, ctx->bound, (rows + ix.tab.size()) * 4));
+    int32_t *dev = ctx->bound.as<int32_t>();
+    HIPCK(hipMemcpyAsync(dev, ix.row.data(), ix.row.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIPCK(hipMemcpyAsync(dev + rows, ix.tab.data(), ix.tab.size() * 4, hipMemcpyHostToDevice,
+                         ctx->stream));
+    HIPCK(hipStreamSynchronize(ctx->stream));
+    ctx->bound_B = B;
+    ctx->bound_n = n;
+    return NAS_OK;
+}
+
+int nas_preempt(nas_ctx *ctx, const int32_t *pods, const int32_t *priority, int32_t n_pods,
+                nas_preemption *out, int32_t *victims_out, int32_t max_victims) {
+    NAS_RANGE("nas_preempt");
+    OK(bind(ctx));
+    OK(no_batch(ctx, "nas_preempt"));
+    if (!ctx->have_cap || !ctx->have_pods || ctx->N <= 0)
+        return nas::fail(ctx, NAS_ERR_STATE, "nas_preempt needs capacity and pods");
+    if (ctx->cap_n != ctx->N || ctx->req_P != ctx->P)
+        return nas::fail(ctx, NAS_ERR_STATE, "nas_preempt: capacity/pods do not match the geometry");
+    if (n_pods < 0 || max_victims < 0 ||
+        (n_pods > 0 && (!out || !priority || (max_victims > 0 && !victims_out))))
+        return nas::fail(ctx, NAS_ERR_ARG,
+                         "nas_preempt: n_pods / priority / out / victims_out / max_victims");
+    if (!pods && n_pods > ctx->P)
+        return nas::fail(ctx, NAS_ERR_ARG,
+                         "nas_preempt: " + std::to_string(n_pods) + " pods asked for, " +
+                             std::to_string(ctx->P) + " are uploaded");
+    if (pods)
+        for (int32_t i = 0; i < n_pods; ++i)
+            if (pods[i] < 0 || pods[i] >= ctx->P)
+                return nas::fail(ctx, NAS_ERR_ARG,
+                                 "nas_preempt: pods[" + std::to_string(i) + "] = " +
+                                     std::to_string(pods[i]) + " is not an uploaded pod");
+    if (ctx->bound_B > 0 && ctx->bound_n != ctx->N)
+        return nas::fail(ctx, NAS_ERR_ARG,
+                         "the bound pods were uploaded for " + std::to_string(ctx->bound_n) +
+                             " nodes, the cluster has " + std::to_string(ctx->N) +
+                             " (nas_upload_bound again)");
+    OK(check_constraints(ctx, ctx->N, ctx->P));
+    if (n_pods == 0) return NAS_OK;
+    OK(prepare_constraints(ctx));
+    if (ctx->bound_B == 0 && ctx->bound_n != ctx->N) {  // no table: every row is empty
+        const size_t bytes = bound_row_ints(ctx->N) * 4;
+        OK(nas::ensure(ctx, ctx->bound, bytes));
+        HIPCK(hipMemsetAsync(ctx->bound.p, 0, bytes, ctx->stream));
+        ctx->bound_n = ctx->N;
+    }
+    // the partials of one launch (at most PART_BYTES of them: a longer list
+    // goes in several launches of whole 64-entry groups), then per list entry
+    // the record, the victims, the pod index and the priority
+    constexpr size_t PART_BYTES = (size_t)64 << 20;
+    const size_t n = (size_t)n_pods, mv = (size_t)max_victims;
+    const size_t slabs = (size_t)nas::preempt_slabs(ctx->N);
+    const size_t per = std::min(
+        n, std::max<size_t>(64, PART_BYTES / (slabs * sizeof(nas::PreemptPart)) / 64 * 64));
+    const size_t part_bytes = per * slabs * sizeof(nas::PreemptPart);
+    const size_t rec_bytes = n * sizeof(nas_preemption), vict_bytes = n * mv * 4;
+    OK(nas::ensure(ctx, ctx->preempt,
+                   part_bytes + rec_bytes + vict_bytes + (pods ? n * 4 : 0) + n * 4));
+    char *base = ctx->preempt.as<char>();
+    nas::PreemptArgs pa;
+    pa.part = reinterpret_cast<nas::PreemptPart *>(base);
+    nas_preemption *rec = reinterpret_cast<nas_preemption *>(base + part_bytes);
+    int32_t *vict = reinterpret_cast<int32_t *>(base + part_bytes + rec_bytes);
+    int32_t *list = pods ? vict + n * mv : nullptr;
+    int32_t *prio = vict + n * mv + (pods ? n : 0);
+    if (pods) HIPCK(hipMemcpyAsync(list, pods, n * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIPCK(hipMemcpyAsync(prio, priority, n * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (mv) HIPCK(hipMemsetAsync(vict, 0xff, vict_bytes, ctx->stream));  // -1
+    pa.cap = ctx->cap.as<int32_t>();
+    pa.N = ctx->N;
+    pa.req = ctx->req.as<int32_t>();
+    pa.rs = ctx->Pp;
+    pa.tab.row = ctx->bound.as<int32_t>();
+    pa.tab.B = ctx->bound_B;
+    if (pa.tab.B > 0) pa.tab.tab = pa.tab.row + bound_row_ints(ctx->bound_n);
+    pa.el = elig(ctx);
+    pa.maxv = max_victims;
+    pa.n_cu = ctx->n_cu;
+    for (size_t at = 0; at < n; at += per) {
+        pa.pods = list ? list + at : nullptr;
+        pa.first = (int)at;
+        pa.prio = prio + at;
+        pa.n = (int)std::min(per, n - at);
+        pa.out = rec + at;
+        pa.vict = mv ? vict + at * mv : nullptr;
+        HIPCK(nas::launch_preempt(ctx->stream, pa));
+    }
+    HIPCK(hipMemcpyAsync(out, rec, rec_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (mv) HIPCK(hipMemcpyAsync(victims_out, vict, vict_bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIPCK(hipStreamSynchronize(ctx->stream));
     return NAS_OK;
 }

@@ -192,6 +192,12 @@ struct nas_ctx {
     nas::DevBuf ref_stage;   // pinned: nas_score_reference results [P] best | [P][6] winners
     nas::DevBuf scratch;
     nas::DevBuf explain;     // nas_explain: [n] records of NAS_WHY_COUNT ints | [n] listed pods
+    // nas_upload_bound / nas_preempt, allocated on their first use: the bound
+    // pods' index (row [bound_n + 1] | tab [BT_ROWS][bound_B]; bound_n == 0: to
+    // be made, as empty rows, for the cluster at hand) and the query's buffers
+    // (partials | records | victims | listed pods | priorities)
+    nas::DevBuf bound, preempt;
+    int32_t bound_B = 0, bound_n = 0;
     // exact int32 traffic (nas::Ovf): entries outside the int8 plane, and Lr
     nas::DevBuf ovf_ptr, ovf_m, ovf_e, Lr;
     int64_t ovf_n = 0;          // entries (0: the plane is the traffic)
@@ -355,6 +361,45 @@ hipError_t launch_fit(hipStream_t st, const FitArgs &a);
 // the grid
 hipError_t launch_explain(hipStream_t st, const int32_t *cap, int N, const int32_t *req, int rs,
                           const int32_t *pods, int n_pods, int32_t *out, const Elig *el, int n_cu);
+
+// k_preempt.hip (nas_preempt).  The bound pods' index as bound_index.h builds
+// it: row[N + 1] offsets and tab[BT_ROWS][B] (B == 0: every row is empty and
+// tab is not read)
+struct BoundTab {
+    const int32_t *row = nullptr;
+    const int32_t *tab = nullptr;
+    int B = 0;
+};
+// one (list entry, node slab) partial: the slab's smallest node key -- k0 = 0
+// without victims, else the top victim priority + 2^31 + 1; k1 = priority_sum;
+// k2 = n_victims << 32 | node; all ones: no candidate -- and its candidate count
+struct PreemptPart {
+    uint64_t k0, k1, k2;
+    int32_t candidates, pad;
+};
+int preempt_slabs(int N);  // node slabs of the scan: `part` holds [slabs][n] partials
+// entries [0, n) of a list: entry i is pod pods[i] (nullptr: pod first + i) of
+// req ([3][rs]) and, with el, of its pod words, with priority prio[i]; over all
+// N nodes of cap ([3][N]).  The scan fills part, the pick writes out[i] and the
+// first min(n_victims, maxv) of vict[i * maxv ..] (the rest is the caller's -1)
+struct PreemptArgs {
+    const int32_t *cap = nullptr;
+    int N = 0;
+    const int32_t *req = nullptr;
+    int rs = 0;
+    const int32_t *pods = nullptr;
+    int first = 0;
+    const int32_t *prio = nullptr;
+    int n = 0;
+    BoundTab tab;
+    const Elig *el = nullptr;
+    PreemptPart *part = nullptr;
+    nas_preemption *out = nullptr;
+    int32_t *vict = nullptr;
+    int maxv = 0;
+    int n_cu = 256;
+};
+hipError_t launch_preempt(hipStream_t st, const PreemptArgs &a);
 
 // source lists keys / bounds [n_lists], `stride` / `bstride` words apart and
 // indexed from pod src_p0; pods [p0, p0 + np) (or the window dyn) merge into

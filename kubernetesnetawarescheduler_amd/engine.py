@@ -416,6 +416,41 @@ class Engine:
         self._ck(self._L.nas_explain(self._h, ptr(idx), n, ptr(out)))
         return out
 
+    def upload_bound(self, node, priority, req):
+        """nas_upload_bound: the running pods -- node [B], priority [B], req
+        (B, 3) as upload_pods -- after upload_capacity.  B == 0 clears them."""
+        node = as_c(node, np.int32).reshape(-1)
+        priority = as_c(priority, np.int32).reshape(-1)
+        req = as_c(req, np.int32).reshape(-1, 3)
+        B = node.shape[0]
+        if priority.shape[0] != B or req.shape[0] != B:
+            raise ValueError("upload_bound: node, priority and req differ in length")
+        cols = [np.ascontiguousarray(req[:, r]) for r in range(3)]
+        self._ck(self._L.nas_upload_bound(self._h, ptr(node), ptr(priority),
+                                          *[ptr(c) for c in cols], B))
+
+    def preempt(self, priority, pods=None, max_victims=0):
+        """nas_preempt: for each listed pod (indices into the uploaded pods, any
+        order, duplicates allowed; None: all of them) with priority[i], the
+        node to take and the lower-priority bound pods to evict there, against
+        the working capacity and the bound pods now.  -> (records, victims):
+        a structured array [n] of _lib.PREEMPTION_DTYPE (node, n_victims,
+        top_priority, candidates, priority_sum) and an int32 (n, max_victims)
+        array of bound-pod indices in walk order, -1 past the victims."""
+        priority = as_c(priority, np.int32).reshape(-1)
+        if pods is None:
+            idx, n = None, self.n_pods
+        else:
+            idx = as_c(pods, np.int32).reshape(-1)
+            n = idx.shape[0]
+        if priority.shape[0] != n:
+            raise ValueError("preempt: one priority per listed pod")
+        rec = np.zeros(n, _lib.PREEMPTION_DTYPE)
+        vict = np.full((n, max_victims), -1, np.int32)
+        self._ck(self._L.nas_preempt(self._h, ptr(idx), ptr(priority), n, ptr(rec),
+                                     ptr(vict) if max_victims else None, max_victims))
+        return rec, vict
+
     def score(self):
         self._ck(self._L.nas_score(self._h))
 

@@ -268,6 +268,75 @@ func (e *nasEngine) Explain(pods []int32) ([][8]int32, error) {
 	return out, nil
 }
 
+// UploadBound tells the engine the running pods: pod b runs on node[b] with
+// priority[b] and holds the three requests.  Call it after the capacity upload
+// (it fixes the node count); an empty table clears it.  The requests are what an
+// eviction gives back on top of the free capacity.
+func (e *nasEngine) UploadBound(node, priority, reqCPU, reqMemKiB, reqPods []int32) error {
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	B := len(node)
+	if len(priority) != B || len(reqCPU) != B || len(reqMemKiB) != B || len(reqPods) != B {
+		return errors.New("UploadBound: sizes")
+	}
+	if B == 0 {
+		return nasErr(e.ctx, C.nas_upload_bound(e.ctx, nil, nil, nil, nil, nil, 0), "nas_upload_bound")
+	}
+	rc := C.nas_upload_bound(e.ctx, (*C.int32_t)(&node[0]), (*C.int32_t)(&priority[0]),
+		(*C.int32_t)(&reqCPU[0]), (*C.int32_t)(&reqMemKiB[0]), (*C.int32_t)(&reqPods[0]), C.int32_t(B))
+	return nasErr(e.ctx, rc, "nas_upload_bound")
+}
+
+// Preemption is one pod's answer of Preempt (nas_preemption of include/nas.h):
+// the node to take (C.NAS_EMPTY: none works even after evictions), how many
+// lower-priority pods go there (0: the pod fits as it is), the highest victim
+// priority, the number of nodes that would do, and the sum over the victims of
+// priority + 2^31.
+type Preemption struct {
+	Node        int32
+	NVictims    int32
+	TopPriority int32
+	Candidates  int32
+	PrioritySum int64
+}
+
+// Preempt answers, for each listed pod (indices into the pods of the last
+// placeBatch, any order) with its priority, where it could run once
+// lower-priority pods are evicted and which ones: kube-scheduler's node choice
+// (lowest highest-victim priority, then smallest priority sum, then fewest
+// victims, then lowest node index) against the capacity the pass left and the
+// UploadBound table.  victims[i] holds the first maxVictims victims of pod i as
+// UploadBound indices, -1 past the last.  Every pod is answered on its own: evict
+// for one answer, upload capacity and bound pods again, place again
+// (INTEGRATION.md).
+func (e *nasEngine) Preempt(pods, priority []int32, maxVictims int) ([]Preemption, [][]int32, error) {
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	n := len(pods)
+	if len(priority) != n || maxVictims < 0 {
+		return nil, nil, errors.New("Preempt: sizes")
+	}
+	if n == 0 {
+		return nil, nil, nil
+	}
+	out := make([]Preemption, n)
+	flat := make([]int32, n*maxVictims)
+	var vp *C.int32_t
+	if len(flat) > 0 {
+		vp = (*C.int32_t)(&flat[0])
+	}
+	rc := C.nas_preempt(e.ctx, (*C.int32_t)(&pods[0]), (*C.int32_t)(&priority[0]), C.int32_t(n),
+		(*C.nas_preemption)(unsafe.Pointer(&out[0])), vp, C.int32_t(maxVictims))
+	if err := nasErr(e.ctx, rc, "nas_preempt"); err != nil {
+		return nil, nil, err
+	}
+	victims := make([][]int32, n)
+	for i := range victims {
+		victims[i] = flat[i*maxVictims : (i+1)*maxVictims]
+	}
+	return out, victims, nil
+}
+
 // placeBatch is the network-aware path: pods drained from podQueue (:129) in
 // arrival order, each with its requests and its traffic (MB, fp32) to
 // already-bound peers as CSR -- peerNode[rowPtr[p]:rowPtr[p+1]] is the node
