@@ -21,9 +21,16 @@
 
 #include "bound_index.h"
 #include "nas_internal.h"
+#include "pass_plan.h"
+#include "result_decode.h"
 
+using nas::decode_cost;
+using nas::decode_int_score;
 using nas::DevBuf;
+using nas::gather_batch;
+using nas::host_out_offset;
 using nas::KC;
+using nas::unpack_range;
 
 // roctx range around every C-ABI entry (rocprofv3 --marker-trace shows the
 // host call that issued each kernel); a no-op call without a profiler
@@ -81,61 +88,6 @@ int ensure(nas_ctx *ctx, DevBuf &b, size_t bytes) {
     } while (0)
 
 namespace {
-
-constexpr int RESCORE_PODS = 1024;  // pods per device-side rescore slot (multiple of COST_BN)
-// dry pods rescored per gathered slot (gathered_slot).  1024, not 4096: a
-// bf16 C3 halt (the last chunk's lists, scored against capacity two chunks
-// stale, run dry in a herd) flags > 4096 pods with STALE_MIN_FIT 2, but the
-// first 1024 of them always let the walk finish -- the slot's cost launch
-// 690 -> 235 us, the halting pass's slots 0.9 -> 0.37 ms (traced); 256 / 512
-// need more slots (profiles/r04_ab_gather_pods.txt)
-// (round 6: 6 tiles = 1,536 pods for C3 -- still one wave of cost workgroups
-// over 40 node tiles -- took 65 instead of 89 slots through the full-range
-// herd but 31.6 instead of 29.4 ms, same box: profiles/r06b_ab_slots.txt)
-constexpr int GATHER_PODS = 1024;
-// a pass with the cost-row cache rescores from cached rows (k_rescore_cached:
-// no cost launch), so its slots take more pods
-constexpr int GATHER_PODS_CACHED = 2048;
-// NAS_OPT_COST_CACHE auto: the previous pass's rescore rounds that turn the
-// cache on, and its largest size (C4 at world 1 would need 100 GB)
-constexpr int CACHE_MIN_ROUNDS = 4;
-constexpr size_t CACHE_MAX_BYTES = (size_t)16 << 30;
-// NAS_OPT_HERD_PLAN auto: rescore rounds of one pass that make its shape a herd
-constexpr int HERD_MIN_ROUNDS = 8;
-// gathered slots behind each chunk's commit in the herd plan
-constexpr int HERD_SLOTS = 1;
-// ... of at most this many pods (they run on the CUs a chunk's wave leaves
-// free, C3: 16, where a 2,048-pod rescore takes ~190 us; 512-pod slots
-// measured no faster and less stable: profiles/r06e_ab_herd.txt)
-constexpr int HERD_SLOT_PODS = 2048;
-constexpr int GATHER_SLOTS_PER_SYNC = 4;  // gathered slots enqueued per host check of the halt word
-constexpr int MAX_SPEC_SLOTS = 8;         // speculative slots at most (nas_place, slot_hint)
-// ... except the second check: a walk still halted after a full batch is
-// usually nearly done (C2: 5 slots), and an idle slot's ~8 launches cost about
-// what one more host round trip does, so the second batch is one slot (C2
-// median 1.17 / 1.07 / 1.04 ms with a second batch of 4 / 2 / 1, same
-// placements).  With the cost-row cache (a herd; an idle slot is 3 launches)
-// 8 slots per check from the fourth on
-int gather_batch(int check, bool cached) {
-    return check == 2 ? 1 : (cached && check > 3) ? 8 : GATHER_SLOTS_PER_SYNC;
-}
-int plan_n_mt(const nas_ctx *ctx);
-// (a one-slot FIRST batch for walks halting near their end helped a 12-pod
-// rescore, 0.39 -> 0.26 ms, but cost bench C1's 3-slot case two extra round
-// trips, 0.39 -> 0.52 ms: with a round trip ~2 idle slots, 4 then 1 is the
-// robust order)
-// pinned staging of nas_place results in host_status: behind the status words
-// of every cluster of a batch (B * STATUS_INTS ints; nas_set_batch allows up to
-// 65535 clusters), page-aligned
-size_t host_out_offset(int B) {
-    const size_t status_bytes = (size_t)std::max(B, 1) * (nas::STATUS_INTS + 4) * 4;
-    return std::max<size_t>(4096, (status_bytes + 4095) & ~(size_t)4095);
-}
-// Rescore slots run only for a walk known to have halted (after the
-// pipeline): an idle gathered slot still costs ~0.1 ms of launches (C3,
-// measured), more than the host round trip a stop costs once the pipeline is
-// done -- the results fetch brings the halt word back with the placements --
-// and scoring against the live capacity makes stops rare.
 
 int bind(nas_ctx *ctx) {
     if (!ctx) return NAS_ERR_ARG;
@@ -413,31 +365,21 @@ int prepare_split(nas_ctx *ctx) {
     return NAS_OK;
 }
 
-// one cost/top-k launch over the main traffic rows (or a row-mapped view)
-// The wide cost tile (256 nodes x 384 pods, 12 waves) for the main scoring
-// pass of one whole cluster with many pods (full launch 3.5% (int8) / 6%
-// (bf16) faster than 256 x 256: profiles/r02_s4_ab_wide*.txt), for batches of
-// clusters (C5: launch frac 0.42 -> 0.45 although a 5,000-pod cluster is
-// 13.02 wide tiles, profiles/r04_ab_narrow_fit_wide.txt) and for node shards,
-// there together with CU-masked streams (below; the wide tile alone lost on
-// shards in round 2: longer workgroups, coarser tails).  Small clusters,
-// rescore windows and row-mapped views keep 256 x 256.
-constexpr int WIDE_MIN_PODS = 32768;
 // On a node shard (world > 1) the scoring streams leave RESERVE_SHARD_CUS
 // CUs per XCD to the commit stream (set_stream_masks), so the merge /
 // exchange / commit chain runs beside the wide cost tile instead of waiting
 // for one of its workgroups to drain (profiles/r04_ab_reserve.txt)
 constexpr int RESERVE_SHARD_CUS = 2;  // per XCD; 3 from 4 ranks, 4 from 8 (shard_reserve)
-bool wide_ok(const nas_ctx *ctx) {
-    const bool shard = ctx->world > 1 || ctx->rehearse > 1;
-    if (ctx->B > 1) return !shard;
-    return ctx->Pp >= WIDE_MIN_PODS || shard;
-}
-int tile_pods(const nas_ctx *ctx) {
-    return wide_ok(ctx) ? nas::cost_tile_pods(ctx->dtype == NAS_DT_F32 ? NAS_DT_BF16 : ctx->dtype)
-                        : nas::COST_BN;
-}
 
+// what the planning (pass_plan.h) reads of the context: nothing rank-local
+nas::PassShape shape_of(const nas_ctx *ctx) {
+    return {ctx->P, ctx->Pp, ctx->N, ctx->B, ctx->world, ctx->rehearse, ctx->n_cu,
+            nas::cost_tile_pods(ctx->dtype == NAS_DT_F32 ? NAS_DT_BF16 : ctx->dtype)};
+}
+bool wide_ok(const nas_ctx *ctx) { return nas::wide_ok(shape_of(ctx)); }
+int tile_pods(const nas_ctx *ctx) { return nas::tile_pods(shape_of(ctx)); }
+
+// one cost/top-k launch over the main traffic rows (or a row-mapped view)
 // A launch over a main pod range (no rescore window, no row map) decides the
 // fit itself from `fit` (k_cost.hip: fused fit), so no k_fit launch sits
 // between two cost launches of a scoring stream; windows keep the k_fit mask.
@@ -858,7 +800,7 @@ int score_range(nas_ctx *ctx, Timer &tm, int p_lo, int p_hi, hipStream_t st = nu
 // stops cost launches, not synchronisations.
 int gathered_slot(nas_ctx *ctx, Timer &tm, hipStream_t st, int ch, int32_t *pub, int hi,
                   int r_max = 0) {
-    const int R = std::min({ctx->cache_active ? GATHER_PODS_CACHED : GATHER_PODS, ctx->Pp,
+    const int R = std::min({ctx->cache_active ? nas::GATHER_PODS_CACHED : nas::GATHER_PODS, ctx->Pp,
                             r_max > 0 ? r_max : ctx->Pp});
     OK(nas::ensure(ctx, ctx->g_words, (size_t)nas::stale_words(ctx->Pp) * 8));
     OK(nas::ensure(ctx, ctx->g_idx, (size_t)R * 4));
@@ -942,11 +884,6 @@ int gathered_slot(nas_ctx *ctx, Timer &tm, hipStream_t st, int ch, int32_t *pub,
     return NAS_OK;
 }
 
-float decode_cost(uint32_t raw, int dtype);
-void unpack_range(int32_t *__restrict__ node_out, float *__restrict__ cost_out,
-                  int64_t *__restrict__ int_score_out, const int32_t *__restrict__ from,
-                  const int32_t *__restrict__ raw_in, int lo, int hi, int dtype, int &unsched);
-
 int no_batch(nas_ctx *ctx, const char *what) {
     if (ctx->B > 1)
         return nas::fail(ctx, NAS_ERR_UNSUPPORTED, std::string(what) + " with a cluster batch");
@@ -959,8 +896,8 @@ int no_batch(nas_ctx *ctx, const char *what) {
 // against the working capacity and the walk resumes from s to hi; a cluster
 // that did not halt costs workgroups that exit at once.
 int rescore_slot(nas_ctx *ctx, hipStream_t st, int hi) {
-    const nas::Dyn dyn{ctx->status.as<int32_t>(), RESCORE_PODS, hi};
-    nas::FitArgs fa = fit_args(ctx, ctx->cap.as<int32_t>(), 0, RESCORE_PODS);
+    const nas::Dyn dyn{ctx->status.as<int32_t>(), nas::RESCORE_PODS, hi};
+    nas::FitArgs fa = fit_args(ctx, ctx->cap.as<int32_t>(), 0, nas::RESCORE_PODS);
     fa.dyn = &dyn;
     fa.batch = ctx->B;
     HIPCK(nas::launch_fit(st, fa));
@@ -1175,175 +1112,6 @@ void inject_stall(nas_ctx *ctx, hipStream_t st) {
     }
 }
 
-// pods per pipelined scoring chunk starting at pod lo: at least 32 pod
-// tiles, and enough tiles that one chunk's cost launch has ~512 workgroups on
-// this rank's node tiles (node shards have few node tiles).  The first chunk
-// is 32 tiles, so the commit stream starts early, and the last is at most
-// about 32, so the commit left after the scoring ends (the serial tail, which
-// matters most on a node shard's short scoring) is short.
-constexpr int CHUNK_WORKGROUPS = 512;  // cost workgroups per big chunk (measured best)
-// a node shard's chunks after the first, on shards of up to
-// SHARD_CHUNKS_MAX_MT node tiles (C3 from G = 4 on)
-constexpr int SHARD_CHUNKS = 6;
-constexpr int SHARD_CHUNKS_MAX_MT = 10;
-// 256-pod units per chunk on the wide tile: 32 tiles of 384 (1,280 workgroups
-// at 40 node tiles, as the 256-pod form's 32-unit chunks); 24 / 33 units
-// measured 0.5-2% slower (profiles/r02_s4_ab_chunk.txt)
-constexpr int CHUNK_TILES_WIDE = 48;
-// node tiles per rank for chunk planning: the LARGEST shard's, the same on
-// every rank (rank shards differ by up to one node, so their own Mp can
-// differ by a tile, e.g. 2,049 nodes over 8 ranks: 256 vs 257 nodes); every
-// rank must plan the same chunks, or their per-chunk all-gathers mismatch
-int plan_n_mt(const nas_ctx *ctx) {
-    const int64_t widest = ((int64_t)ctx->N + ctx->world - 1) / ctx->world;
-    return (int)(nas::round_up(std::max<int64_t>(widest, 1), nas::COST_BM) / nas::COST_BM);
-}
-
-int chunk_pods(const nas_ctx *ctx, int c, int lo) {
-    const int wgs = CHUNK_WORKGROUPS;
-    const int n_mt = plan_n_mt(ctx);
-    const int big = std::max(32, (wgs + n_mt - 1) / n_mt);
-    // 32-tile chunks (whole waves of workgroups at 8+ node tiles) with a
-    // short last one; when the workgroup target sets the size (a node shard
-    // with few node tiles), equal chunks: on rank 0 of a G = 8 rehearsal
-    // 1.45 ms vs 1.56 ms per C3 pass, while at G = 1 the 32-tile form is
-    // 2.5% ahead (8.15 vs 8.37 ms)
-    const int mode = big > 32 ? 2 : 0;
-    const int left = (ctx->P - lo + nas::COST_BN - 1) / nas::COST_BN;  // pod tiles left
-    int tiles = c == 0 ? 32 : big;
-    // (one cluster, G = 1) the wide tile's chunks: the first chunk of the
-    // second scoring stream is half as long, so the two streams' chunk
-    // boundaries stay half a chunk apart -- a stream's next chunk waits for
-    // its previous one to complete, and while that drains its last round the
-    // other stream still has undispatched workgroups to fill the CUs (with
-    // equal chunks both streams drained together: ~20 us of idle CUs per
-    // chunk pair in the C3 pass timeline)
-    if (tile_pods(ctx) != nas::COST_BN && ctx->world == 1)
-        tiles = c == 1 ? CHUNK_TILES_WIDE / 2 : CHUNK_TILES_WIDE;
-    // a pass whose pods fit one big chunk (C2: 40 pod tiles on 4 node tiles)
-    // is one chunk: pipelining its short tail would save less than the
-    // cross-stream hops and launches it adds (device time 0.96 -> 0.92 ms, C2)
-    if (c == 0 && left <= big) tiles = left;
-    if (mode == 0) {
-        // a big last chunk is split in two so that the last is 32 tiles (unless
-        // the first part would be a sliver of under 16)
-        if (c > 0 && left > 32 && left <= big && left - 32 >= 16) tiles = left - 32;
-    } else if (mode == 2 && c > 0) {
-        // the rest in equal chunks: SHARD_CHUNKS of them (counting from
-        // chunk 1; fewer when a chunk would drop below 32 units) on shards of
-        // up to SHARD_CHUNKS_MAX_MT node tiles, else of at most `big` tiles
-        // (~512 workgroups).  Six measured best on the C3 rehearsal: G = 8
-        // 1.213 vs 1.227 ms, G = 4 2.105 vs 2.174 ms, but G = 3 (14 node
-        // tiles, 560-workgroup chunks) 2.850 vs 2.812 ms; three to seven
-        // swept (profiles/r05ab_ab_shard_chunks.txt).  (A short last chunk of
-        // 16 / 32 tiles, to shorten the commit left after the scoring,
-        // measured 7-13% slower at G = 8 and 2-3% at G = 4: one more chunk
-        // costs more cross-stream hops than its shorter commit saves)
-        //  the six-way split is capped at 2 x `big` tiles per chunk
-        // (~1,024 workgroups), so a much larger P keeps chunks -- and the
-        // serial merge / exchange / commit of the tail chunk after the
-        // scoring -- bounded instead of growing linearly with P; C3's plans
-        // are unchanged (G = 4: 60-tile chunks under a 104-tile cap, G = 8:
-        // 60 under 206)
-        const int n = n_mt <= SHARD_CHUNKS_MAX_MT
-                          ? std::max({1, std::min(SHARD_CHUNKS - c + 1, left / 32),
-                                      (left + 2 * big - 1) / (2 * big)})
-                          : (left + big - 1) / big;
-        tiles = (left + n - 1) / n;
-    }  // (decreasing chunk sizes n, n-1, ..., 1 measured 7-10% slower at G = 4 / 8)
-    // whole cost tiles per chunk: the wide tile (384 pods) needs multiples of
-    // 3 units, or a chunk's last tile would score pods of the next chunk
-    const int unit = tile_pods(ctx) / std::gcd(tile_pods(ctx), nas::COST_BN);
-    tiles = std::min(left, (tiles + unit - 1) / unit * unit);
-    return tiles * nas::COST_BN;
-}
-
-// The pass's scoring chunks [lo, hi) in pod order; chunk c runs on scoring
-// stream c & 1.  On the wide tile (one cluster, G = 1) the two streams'
-// totals are balanced at the end: the remainder after the 48-unit chunks is
-// split over one last chunk per stream, sized so that both streams carry the
-// same number of units and finish together (with the last chunks alternating
-// as before, the stream that drew the first full chunk carried ~37 more wide
-// tiles of 261 at C3, and ran alone -- one partial wave of idle CUs per
-// chunk -- for the last ~1.4 ms of the scoring: profiles/r03_pass_timeline_c3_*.txt,
-// r03_ab_balance_ksweep.txt)
-// Node shards keep equal chunks (chunk_pods mode 2): the balanced plan put
-// two chunk chains in the pass's tail and measured 4-8% slower at G = 8 and
-// 1% at G = 4 (profiles/r03_ab_chunk_plan_shard.txt).  Putting the half-length
-// chunk first (chunks then finish in pod order) measured the same or 0.5%
-// slower, and so did moving units from a stream's short last chunk to its
-// previous one (r03_ab_chunk_order.txt).
-std::vector<std::pair<int, int>> plan_chunks(const nas_ctx *ctx, bool herd = false) {
-    std::vector<std::pair<int, int>> chunks;
-    const int P = ctx->P;
-    const bool wide = tile_pods(ctx) != nas::COST_BN && ctx->world == 1;
-    if (herd) {
-        // the herd plan's chunks (nas_place): ONE wave of cost workgroups
-        // each -- as many pod tiles as the CUs hold beside this rank's node
-        // tiles (C3: 6 wide tiles = 2,304 pods over 40 node tiles = 240
-        // workgroups), so the commit stream keeps the CUs left over -- and at
-        // most ~1.25 pods per node (a chunk's own pods compete for the nodes
-        // its fit saw free; tools/herd_model.py: 0 slots at 3,072 pods per
-        // chunk, 5 at 6,144, 18 at 12,288 for 36,864 pods over 10k nodes)
-        const int tp = tile_pods(ctx);
-        int tiles = std::min(ctx->n_cu / std::max(plan_n_mt(ctx), 1),
-                             std::max(1, (int)((5LL * ctx->N / 4) / tp)));
-        if (tp != nas::COST_BN) tiles = std::max(2, tiles / 2 * 2);  // whole 256-pod units
-        tiles = std::max(tiles, 1);
-        const int step = tiles * tp;
-        for (int lo = 0; lo < P; lo += step) chunks.push_back({lo, std::min(P, lo + step)});
-        return chunks;
-    }
-    if (!wide) {
-        for (int c = 0, lo = 0; lo < P; ++c) {
-            const int hi = std::min(P, lo + chunk_pods(ctx, c, lo));
-            chunks.push_back({lo, hi});
-            lo = hi;
-        }
-        return chunks;
-    }
-    const int unit = tile_pods(ctx) / std::gcd(tile_pods(ctx), nas::COST_BN);  // wide: 3 (256-pod units)
-    const int total = (P + nas::COST_BN - 1) / nas::COST_BN;                   // 256-pod units
-    std::vector<int> sizes;
-    int load[2] = {0, 0}, left = total;
-    auto take = [&](int u) {
-        u = std::min(left, (u + unit - 1) / unit * unit);
-        sizes.push_back(u);
-        load[(sizes.size() - 1) & 1] += u;
-        left -= u;
-    };
-    // 48-unit chunks, the second stream's first one half as long
-    const int big = CHUNK_TILES_WIDE;
-    if (left <= big) {
-        take(left);
-    } else {
-        take(big);
-        take(big / 2);
-        while (left > 0) {
-            // can the rest end as one chunk on the next stream s and one on
-            // the other, both at most `big`, with equal stream totals?
-            const int s = sizes.size() & 1;
-            const int x = std::max(0, (left + load[s ^ 1] - load[s]) / 2) / unit * unit;
-            if (x >= unit && x <= big && left - x <= big) {
-                take(x);
-                if (left > 0) take(left);
-                break;
-            }
-            if (x < unit && left <= big) {  // stream s is ahead: one last chunk
-                take(left);
-                break;
-            }
-            take(big);
-        }
-    }
-    for (int lo = 0, i = 0; i < (int)sizes.size(); ++i) {
-        const int hi = std::min(P, lo + sizes[i] * nas::COST_BN);
-        chunks.push_back({lo, hi});
-        lo = hi;
-    }
-    return chunks;
-}
-
 int alloc_extended(nas_ctx *ctx) {
     const size_t chunks = ctx->Mp / 64, B = ctx->B;
     OK(nas::ensure(ctx, ctx->mask, B * chunks * ctx->Pp * 8));
@@ -1375,50 +1143,6 @@ int alloc_extended(nas_ctx *ctx) {
         ctx->host_status.bytes = hs_bytes;
     }
     return NAS_OK;
-}
-
-void unpack_range(int32_t *__restrict__ node_out, float *__restrict__ cost_out,
-                  int64_t *__restrict__ int_score_out, const int32_t *__restrict__ from,
-                  const int32_t *__restrict__ raw_in, int lo, int hi, int dtype, int &unsched) {
-    const uint32_t *__restrict__ raw = reinterpret_cast<const uint32_t *>(raw_in);
-    int none = 0;
-    if (dtype == NAS_DT_I8 && cost_out && int_score_out) {
-        // the common case in one pass over the stage (host-memory bound:
-        // 24 B per pod; 0.24 vs 0.49 ms per 100k pods for the per-pod loop
-        // with the dtype test and a possibly aliased counter inside)
-        for (int i = lo; i < hi; ++i) {
-            const int32_t n = from[i];
-            const int32_t v = (int32_t)(raw[i] ^ 0x80000000u);
-            const bool z = n < 0;
-            node_out[i] = n;
-            none += z;
-            cost_out[i] = z ? 0.f : (float)v;
-            int_score_out[i] = z ? 0 : (int64_t)v;
-        }
-        unsched += none;
-        return;
-    }
-    std::memcpy(node_out + lo, from + lo, (size_t)(hi - lo) * 4);
-    for (int i = lo; i < hi; ++i) none += from[i] < 0;
-    unsched += none;
-    if (cost_out)
-        for (int i = lo; i < hi; ++i) cost_out[i] = from[i] < 0 ? 0.f : decode_cost(raw[i], dtype);
-    if (int_score_out) {
-        if (dtype == NAS_DT_I8) {
-            for (int i = lo; i < hi; ++i)
-                int_score_out[i] = from[i] < 0 ? 0 : (int64_t)(int32_t)(raw[i] ^ 0x80000000u);
-        } else {
-            std::memset(int_score_out + lo, 0, (size_t)(hi - lo) * 8);
-        }
-    }
-}
-
-float decode_cost(uint32_t raw, int dtype) {
-    if (dtype == NAS_DT_I8) return (float)(int32_t)(raw ^ 0x80000000u);
-    const uint32_t u = (raw & 0x80000000u) ? (raw & 0x7fffffffu) : ~raw;
-    float f;
-    std::memcpy(&f, &u, 4);
-    return f;
 }
 
 void destroy_comms(nas_ctx *ctx) {
@@ -2701,36 +2425,6 @@ int nas_place(nas_ctx *ctx, int32_t *node_out, float *cost_out, int64_t *int_sco
     hipStream_t st = ctx->stream, sc = ctx->stream_commit;
     const int P = ctx->P, N = ctx->N;
     int32_t *halt = ctx->status.as<int32_t>();
-    // The cost-row cache (NAS_OPT_COST_CACHE, k_rescore_cached): in auto mode
-    // when the previous pass of this shape needed CACHE_MIN_ROUNDS rescore
-    // rounds or more (a herd: consecutive passes over similar clusters stop
-    // alike, as the speculative slots below assume too).  It costs the main
-    // cost launches a 4-byte store per (pod, node) and saves every gathered
-    // slot its fit / cost / merge launches.  Same placements either way.
-    struct CacheOff {
-        nas_ctx *c;
-        ~CacheOff() { c->cache_active = false; }
-    } cache_off{ctx};
-    ctx->cache_active = false;
-    // (the herd plan below, auto: sticky for a shape once one of its passes
-    // needed HERD_MIN_ROUNDS rescore rounds; it turns the cache on too)
-    const bool herd_shape = !has_coll(ctx) &&
-                            (ctx->opt_herd_plan == 1 ||
-                             (ctx->opt_herd_plan == 2 && ctx->herd_P == P && ctx->herd_N == N));
-    // (not with node selectors / taints: k_rescore_cached rebuilds lists from
-    // cached rows against capacity alone.  The constraints are replicated, so
-    // every rank of a communicator decides alike; the slots recompute through
-    // the constrained k_fit, whatever NAS_OPT_COST_CACHE says)
-    if (ctx->opt_cost_cache != 0 && !constrained(ctx)) {
-        const bool herd = ctx->slot_hint_P == P && ctx->slot_hint_N == N &&
-                          ctx->last_rescore_rounds >= CACHE_MIN_ROUNDS;
-        const size_t bytes = (size_t)ctx->Pp * ctx->Mp * 4;
-        if ((ctx->opt_cost_cache == 1 || herd || herd_shape) && bytes <= CACHE_MAX_BYTES)
-            ctx->cache_active = nas::ensure(ctx, ctx->cost_cache, bytes) == NAS_OK;
-        if (!ctx->cache_active) ctx->err.clear();  // (no memory: the slots recompute)
-    }
-    const bool herd = herd_shape;
-    hipEvent_t t0 = tm.mark(st);
     // Each chunk is filtered against the working capacity as the commit
     // stream has left it so far: every value read is >= the capacity at the
     // chunk's pods' own (later) turn, so every node that will fit them is
@@ -2740,6 +2434,28 @@ int nas_place(nas_ctx *ctx, int32_t *node_out, float *cost_out, int64_t *int_sco
     // below them, so it also maintains a published copy (cap_snap, start
     // minus committed pods) that scoring reads instead.
     const bool live_cap = nas::commit_in_lds(N);
+    // The pass's plan -- herd or pipelined, its chunks, which streams carry
+    // what -- decided here, before any enqueue, from the shape, the options,
+    // what earlier passes left and this context's predicates (pass_plan.h,
+    // where each flag is explained); the loops below only read it.
+    const size_t cache_bytes = (size_t)ctx->Pp * ctx->Mp * 4;
+    const nas::PassPlan plan = nas::plan_pass(
+        shape_of(ctx),
+        {ctx->opt_herd_plan, ctx->opt_cost_cache, ctx->opt_inject_stall_ms, ctx->opt_commit_wait_ms,
+         ctx->opt_comm_timeout_ms, ctx->hist, has_coll(ctx), exchanging(ctx), constrained(ctx),
+         live_cap, cache_bytes});
+    const std::vector<std::pair<int, int>> &chunks = plan.chunks;
+    // the cost-row cache for this pass (plan.want_cache), if there is memory
+    struct CacheOff {
+        nas_ctx *c;
+        ~CacheOff() { c->cache_active = false; }
+    } cache_off{ctx};
+    ctx->cache_active = false;
+    if (plan.want_cache) {
+        ctx->cache_active = nas::ensure(ctx, ctx->cost_cache, cache_bytes) == NAS_OK;
+        if (!ctx->cache_active) ctx->err.clear();  // (no memory: the slots recompute)
+    }
+    hipEvent_t t0 = tm.mark(st);
     const int32_t *score_cap = live_cap ? ctx->cap.as<int32_t>() : ctx->cap_snap.as<int32_t>();
     int32_t *pub = live_cap ? nullptr : ctx->cap_snap.as<int32_t>();
     // one launch: halt = -1, rescores / rounds / slot control = 0 (and the
@@ -2758,16 +2474,7 @@ int nas_place(nas_ctx *ctx, int32_t *node_out, float *cost_out, int64_t *int_sco
     const bool want_raw = cost_out || int_score_out;
     struct Landed { int lo, hi; hipEvent_t ev; };
     std::vector<Landed> landed;
-    // chunk bounds; every scoring launch is enqueued before any commit-stream
-    // work, so the host's enqueue time of merges / commits / copies never
-    // delays the next chunk's cost launch
-    const std::vector<std::pair<int, int>> chunks = plan_chunks(ctx, herd);
-    // a one-chunk pass without a communicator has nothing to pipeline: its
-    // merge / commit / copies stay on the scoring stream, which saves the
-    // cross-stream event hops (~15-20 us each) that dominate a small pass
-    // (C1 extended 0.41 -> 0.385 ms per nas_place)
-    const bool one_stream = chunks.size() == 1 && !has_coll(ctx);
-    if (one_stream) sc = st;
+    if (plan.one_stream) sc = st;
     // With the LDS commit nothing the scoring kernels read comes from the
     // pass init (capacity is read live), so the first chunk's fit and cost are
     // the first launches of the pass and the init goes to the commit stream
@@ -2778,28 +2485,6 @@ int nas_place(nas_ctx *ctx, int32_t *node_out, float *cost_out, int64_t *int_sco
     // above (overflow lists, latency rows, fp32 splits) are read by every
     // chunk's cost launch.
     if (!live_cap) OK(pass_init(st));
-    // the two scoring streams (on a node shard CU-masked by set_stream_masks:
-    // they leave 2-3 CUs per XCD to the commit stream, profiles/r04_ab_reserve.txt;
-    // round 3's masks that reserved 8-16 CUs beside the narrow tile measured
-    // 25-35% slower, r03_ab_reserve_cus.txt)
-    const int spec = (!herd && !has_coll(ctx) && ctx->slot_hint_P == P && ctx->slot_hint_N == N)
-                         ? ctx->slot_hint : 0;
-    // (the herd plan's slots run inside its chunk loop, behind each commit;
-    // pods they place after their chunk's rows were staged are unpacked again
-    // at the end, like the speculative slots' -- `late_slots`)
-    const bool late_slots = spec > 0 || herd;
-    // (an injected stall, NAS_OPT_INJECT_STALL_MS, sits on st behind the
-    // pass: the host must wait on st then)
-    // (the pass's last commit writes the status words to the pinned host area)
-    const bool status_in_commit = !late_slots && ctx->opt_inject_stall_ms == 0;
-    // its bound: with collectives the communicator deadline -- the
-    // commit stream's last commit may wait on an all-gather whose peer died --
-    // so the pass fails as a communicator failure (below), never with a
-    // shorter fixed budget that makes the tail "complete" while RCCL is stuck
-    const int64_t commit_wait_ms =
-        ctx->opt_commit_wait_ms > 0 ? ctx->opt_commit_wait_ms
-        : has_coll(ctx)             ? (ctx->opt_comm_timeout_ms > 0 ? ctx->opt_comm_timeout_ms : 600000)
-                                    : 2000;
     // a chunk's commit (both plans): the walk stages the chunk's rows itself;
     // the pass's last commit also writes the status words into the pinned
     // host area when nothing follows it (no speculative slots): the host
@@ -2809,11 +2494,11 @@ int nas_place(nas_ctx *ctx, int32_t *node_out, float *cost_out, int64_t *int_sco
         cm.pub = pub;
         cm.stage_node = stage;
         cm.stage_cost = want_raw ? stage + P : nullptr;
-        cm.stage_status = last && status_in_commit ? hs : nullptr;
+        cm.stage_status = last && plan.status_in_commit ? hs : nullptr;
         HIPCK(nas::launch_commit(s, cm));
         return NAS_OK;
     };
-    if (herd) {
+    if (plan.herd) {
         // The herd plan: chunks of one wave of cost workgroups, scored and
         // merged back to back on one stream; each chunk's commit and
         // HERD_SLOTS gathered slots run on the commit stream, on the CUs that
@@ -2845,14 +2530,18 @@ int nas_place(nas_ctx *ctx, int32_t *node_out, float *cost_out, int64_t *int_sco
             // slots or the host loop below); idle slots are three launches
             // that exit at once
             if (ctx->cache_active)
-                for (int r = 0; r < HERD_SLOTS; ++r)
-                    OK(gathered_slot(ctx, tm, sc, CH_SCORE, pub, hi, HERD_SLOT_PODS));
+                for (int r = 0; r < nas::HERD_SLOTS; ++r)
+                    OK(gathered_slot(ctx, tm, sc, CH_SCORE, pub, hi, nas::HERD_SLOT_PODS));
             landed.push_back({lo, hi, tm.mark(sc)});
         }
         HIPCK(hipStreamWaitEvent(st, tm.mark(sc), 0));
     } else {
+        // the two scoring streams (on a node shard CU-masked by set_stream_masks:
+        // they leave 2-3 CUs per XCD to the commit stream, profiles/r04_ab_reserve.txt;
+        // round 3's masks that reserved 8-16 CUs beside the narrow tile measured
+        // 25-35% slower, r03_ab_reserve_cus.txt)
         const hipStream_t ss2[2] = {st, ctx->stream2};
-        if (!one_stream) {
+        if (!plan.one_stream) {
             hipEvent_t ready = tm.mark(st);
             for (hipStream_t s : {ss2[0], ss2[1], sc})
                 if (s != st) HIPCK(hipStreamWaitEvent(s, ready, 0));
@@ -2868,15 +2557,10 @@ int nas_place(nas_ctx *ctx, int32_t *node_out, float *cost_out, int64_t *int_sco
             OK(score_range(ctx, tm, chunks[c].first, chunks[c].second, ss, score_cap, false));
             // (one stream: nothing waits on it -- every event record or wait is a
             // packet the queue processes between two kernels)
-            scored[c] = one_stream ? nullptr : tm.mark(ss);
+            scored[c] = plan.one_stream ? nullptr : tm.mark(ss);
         }
-        // (one stream: the chunk's merge starts the status words itself)
-        const bool init_in_merge = one_stream && live_cap;
-        if (live_cap && !init_in_merge) OK(pass_init(sc));
-        // speculative slots: as many as the previous pass of this shape needed
-        // (consecutive passes over similar clusters stop alike), enqueued before
-        // the first status round trip; a slot whose walk is not halted exits at
-        // once.  Not with a communicator: every rank must issue the same slots.
+        if (live_cap && !plan.init_in_merge) OK(pass_init(sc));
+        // (plan.xs_mode)
         // A node-shard pass's chunks merge and exchange on their own stream (sx,
         // the commit stream's communicator and CUs) and the commit stream only
         // commits, each commit waiting for its chunk's merged lists: with every
@@ -2888,7 +2572,6 @@ int nas_place(nas_ctx *ctx, int32_t *node_out, float *cost_out, int64_t *int_sco
         // stream's own communicator and gather buffers, so the collectives of
         // each communicator stay on one stream in one order) and commits there
         // after the commit stream's last commit.
-        const bool xs_mode = exchanging(ctx) && !one_stream;
         // the tail chunk's stream waits for the commit stream's last commit: by
         // the device word behind each commit (launch_flag_set / flag_wait) once a
         // commit has run on the commit stream, else by an event (a one-chunk pass
@@ -2896,12 +2579,12 @@ int nas_place(nas_ctx *ctx, int32_t *node_out, float *cost_out, int64_t *int_sco
         auto *cflag = ctx->commit_flag.as<uint64_t>();
         auto after_commits = [&](hipStream_t s) -> int {
             if (chunks.size() > 1)
-                HIPCK(nas::launch_flag_wait(s, cflag, ctx->commit_seq, halt, commit_wait_ms));
+                HIPCK(nas::launch_flag_wait(s, cflag, ctx->commit_seq, halt, plan.commit_wait_ms));
             else HIPCK(hipStreamWaitEvent(s, tm.mark(sc), 0));
             return NAS_OK;
         };
         hipStream_t sx = nullptr;
-        if (xs_mode) OK(exchange_stream(ctx, &sx));
+        if (plan.xs_mode) OK(exchange_stream(ctx, &sx));
         for (size_t c = 0; c < chunks.size(); ++c) {
             const int lo = chunks[c].first, hi = chunks[c].second;
             // the last chunk is merged and committed on its own scoring stream
@@ -2909,10 +2592,10 @@ int nas_place(nas_ctx *ctx, int32_t *node_out, float *cost_out, int64_t *int_sco
             // the pass's serial tail after the last cost launch has no
             // cross-stream hop in front of its merge (the communicator is the
             // commit stream's: its collectives stay in one order)
-            const bool tail = !one_stream && c + 1 == chunks.size();
+            const bool tail = !plan.one_stream && c + 1 == chunks.size();
             const bool last = c + 1 == chunks.size();
             hipStream_t cs = sc;
-            if (xs_mode) {
+            if (plan.xs_mode) {
                 if (tail) {
                     cs = ss2[c & 1];
                     OK(merge_range(ctx, tm, lo, hi, cs, (c & 1) ? CH_SCORE2 : CH_SCORE, (int)(c & 1)));
@@ -2926,18 +2609,18 @@ int nas_place(nas_ctx *ctx, int32_t *node_out, float *cost_out, int64_t *int_sco
                 if (tail) {
                     cs = ss2[c & 1];
                     OK(after_commits(cs));
-                } else if (!one_stream) {
+                } else if (!plan.one_stream) {
                     HIPCK(hipStreamWaitEvent(sc, scored[c], 0));
                 }
                 // (merging the tail chunk locally before this wait, gated before
                 // its exchange / commit, measured within noise at G = 1 and 8:
                 // profiles/r04_ab_tail.txt)
-                OK(merge_range(ctx, tm, lo, hi, cs, CH_COMMIT, 0, init_in_merge ? halt : nullptr));
+                OK(merge_range(ctx, tm, lo, hi, cs, CH_COMMIT, 0, plan.init_in_merge ? halt : nullptr));
             }
             hipEvent_t c0 = tm.fine(cs);
             OK(commit_chunk(cs, lo, hi, last));
             // (releases the tail chunk's commit)
-            if (!one_stream && !last) {
+            if (!plan.one_stream && !last) {
                 if (c + 2 == chunks.size() && ctx->opt_inject_commit_stall_ms > 0) {
                     (void)nas::launch_stall(cs, ctx->opt_inject_commit_stall_ms);  // (test option)
                     ctx->opt_inject_commit_stall_ms = 0;
@@ -2961,15 +2644,15 @@ int nas_place(nas_ctx *ctx, int32_t *node_out, float *cost_out, int64_t *int_sco
         // stream, which followed every earlier chunk's scoring (and, with xs_mode,
         // every earlier chunk's exchange); so st waits only when the last chunk
         // ran on another stream
-        if (!one_stream && ss2[(chunks.size() - 1) & 1] != st)
+        if (!plan.one_stream && ss2[(chunks.size() - 1) & 1] != st)
             HIPCK(hipStreamWaitEvent(st, tm.mark(ss2[(chunks.size() - 1) & 1]), 0));
         // (the tail followed the commit stream by the device word, not a stream
         // wait: st follows the commit stream itself)
-        if (!one_stream && chunks.size() > 1) HIPCK(hipStreamWaitEvent(st, tm.mark(sc), 0));
+        if (!plan.one_stream && chunks.size() > 1) HIPCK(hipStreamWaitEvent(st, tm.mark(sc), 0));
     }
     if (has_coll(ctx)) inject_stall(ctx, st);  // behind every collective of the pass
-    for (int r = 0; r < spec; ++r) OK(gathered_slot(ctx, tm, st, CH_SCORE, nullptr, P));
-    if (late_slots) {
+    for (int r = 0; r < plan.spec; ++r) OK(gathered_slot(ctx, tm, st, CH_SCORE, nullptr, P));
+    if (plan.late_slots) {
         // behind the slots, all placements again: when they finished the walk,
         // the status round trip below brings the final results with it
         HIPCK(hipMemcpyAsync(stage_spec, ctx->out_node.p, (size_t)P * 4, hipMemcpyDeviceToHost,
@@ -3003,7 +2686,7 @@ int nas_place(nas_ctx *ctx, int32_t *node_out, float *cost_out, int64_t *int_sco
     // host unpacks each chunk as its copy lands.  Values copied behind a commit
     // are final unless the walk halted there -- then (rare) more slots run and
     // everything is fetched and unpacked again.
-    if (status_in_commit) {
+    if (plan.status_in_commit) {
         t1 = landed.back().ev;  // the last commit wrote hs itself
     } else {
         HIPCK(hipMemcpyAsync(hs, halt, NSTAT * 4, hipMemcpyDeviceToHost, st));
@@ -3015,7 +2698,7 @@ int nas_place(nas_ctx *ctx, int32_t *node_out, float *cost_out, int64_t *int_sco
     }
     OK(wait_event(ctx, t1));  // t1 follows the status words (copy, or the last commit)
     int checks = 0;
-    if (late_slots && hs[0] < 0 && hs[1] > 0) {
+    if (plan.late_slots && hs[0] < 0 && hs[1] > 0) {
         // speculative slots finished a walk that had halted: the per-chunk
         // copies behind the commits predate them; the full copy behind the
         // slots (same round trip, its own staging area) holds the final
@@ -3037,7 +2720,7 @@ int nas_place(nas_ctx *ctx, int32_t *node_out, float *cost_out, int64_t *int_sco
         // deadline does (the stuck collective kernels return, so the streams
         // drain and nas_destroy cannot block on them)
         const std::string why = "the last commit's wait for the commit stream exceeded " +
-                                std::to_string(commit_wait_ms) + " ms";
+                                std::to_string(plan.commit_wait_ms) + " ms";
         if (has_coll(ctx)) {
             abort_comms(ctx);
             return nas::fail(ctx, NAS_ERR_COMM,
@@ -3051,7 +2734,7 @@ int nas_place(nas_ctx *ctx, int32_t *node_out, float *cost_out, int64_t *int_sco
         if (++checks > P + 1) return nas::fail(ctx, NAS_ERR_HIP, "commit made no progress");
         // (with speculative slots the walk may have resumed and halted again:
         // its first halt is status word 3)
-        if (h0 < 0) h0 = late_slots ? (hs[1] > 0 ? std::min(std::max(hs[3], 0), hs[0]) : hs[0]) : hs[0];
+        if (h0 < 0) h0 = plan.late_slots ? (hs[1] > 0 ? std::min(std::max(hs[3], 0), hs[0]) : hs[0]) : hs[0];
         for (int r = 0, n = gather_batch(checks, ctx->cache_active); r < n; ++r)
             OK(gathered_slot(ctx, tm, st, CH_SCORE, nullptr, P));
         OK(fetch());
@@ -3067,14 +2750,7 @@ int nas_place(nas_ctx *ctx, int32_t *node_out, float *cost_out, int64_t *int_sco
     ctx->timings.rescored_pods = hs[RESCORED];
     ctx->timings.unschedulable = unsched;
     ctx->timings.commit_rounds = hs[2];
-    ctx->slot_hint = std::min(hs[1], MAX_SPEC_SLOTS);
-    ctx->last_rescore_rounds = hs[1];
-    if (hs[1] >= HERD_MIN_ROUNDS) {
-        ctx->herd_P = P;
-        ctx->herd_N = N;
-    }
-    ctx->slot_hint_P = P;
-    ctx->slot_hint_N = N;
+    nas::note_pass(ctx->hist, P, N, hs[1]);
     ctx->scored = true;
     return NAS_OK;
 }
@@ -3102,7 +2778,7 @@ int nas_get_candidates(nas_ctx *ctx, int32_t *cand_node, int64_t *cand_cost_i, f
             const uint32_t raw = (uint32_t)(k >> 32);
             if (cand_cost_i)
                 cand_cost_i[(size_t)p * KC + j] =
-                    (ok && ctx->dtype == NAS_DT_I8) ? (int64_t)(int32_t)(raw ^ 0x80000000u) : 0;
+                    (ok && ctx->dtype == NAS_DT_I8) ? (int64_t)decode_int_score(raw) : 0;
             if (cand_cost_f) cand_cost_f[(size_t)p * KC + j] = ok ? decode_cost(raw, ctx->dtype) : 0.f;
         }
         if (count) count[p] = c;
@@ -3216,7 +2892,7 @@ int nas_commit(nas_ctx *ctx, int32_t p_begin, int32_t *node_out, float *cost_out
         if (cost_out) cost_out[p_begin + i] = none ? 0.f : decode_cost(raw[i], ctx->dtype);
         if (int_score_out)
             int_score_out[p_begin + i] = (none || ctx->dtype != NAS_DT_I8)
-                                             ? 0 : (int64_t)(int32_t)(raw[i] ^ 0x80000000u);
+                                             ? 0 : (int64_t)decode_int_score(raw[i]);
     }
     *stop_out = stop;
     tm.report_stages();  // (only the commit booked a span)

@@ -113,6 +113,17 @@ struct LocalSrcs {
 struct LocalGroup;  // nas_api.hip
 struct CommInit;    // nas_api.hip: state shared with a nas_comm_init helper thread
 
+// What one nas_place leaves for the planning of the next (pass_plan.h:
+// plan_pass reads it, note_pass writes it).
+struct PassHistory {
+    // auto (NAS_OPT_HERD_PLAN 2): the shape whose passes run the herd plan
+    int32_t herd_P = -1, herd_N = -1;
+    // gathered slots the previous nas_place of shape (P, N) needed: enqueued
+    // speculatively by the next pass of that shape
+    int32_t slot_hint = 0, slot_hint_P = -1, slot_hint_N = -1;
+    int32_t last_rescore_rounds = 0;  // of the previous nas_place of shape (slot_hint_P, _N)
+};
+
 }  // namespace nas
 
 struct nas_ctx {
@@ -137,10 +148,7 @@ struct nas_ctx {
     nas::DevBuf snap[6];              // cpu, mem, bw (f64) ; rx, tx, disk (i64)  [S][ns]
     int32_t n_orders = 0;
     bool orders_per_pod = false;      // nas_upload_pod_orders: set p belongs to pod p
-    // gathered slots the previous nas_place of shape (P, N) needed: enqueued
-    // speculatively by the next pass of that shape
-    int32_t slot_hint = 0, slot_hint_P = -1, slot_hint_N = -1;
-    int32_t last_rescore_rounds = 0;  // of the previous nas_place of shape (slot_hint_P, _N)
+    nas::PassHistory hist;
     // cost-row cache (NAS_OPT_COST_CACHE): [Pp][Mp] orderable keys of the
     // current pass's main cost launches, read by its gathered rescore slots
     nas::DevBuf cost_cache;
@@ -261,7 +269,6 @@ struct nas_ctx {
     int32_t opt_commit_cus = 0;             // NAS_OPT_COMMIT_CUS (world 1)
     int32_t opt_cost_cache = 2;             // NAS_OPT_COST_CACHE: 0 off, 1 on, 2 auto
     int32_t opt_herd_plan = 2;              // NAS_OPT_HERD_PLAN: 0 off, 1 on, 2 auto
-    int32_t herd_P = -1, herd_N = -1;       // auto: the shape whose passes run the herd plan
     bool poisoned = false;       // a collective missed its deadline: communicators aborted
     // timing events, created once and reused by every call (hipEventCreate
     // per mark cost a small placement more than its kernels)

@@ -16,7 +16,7 @@ import numpy as np
 from . import _lib
 
 KEY_INVALID = np.uint64(0xFFFFFFFFFFFFFFFF)
-RESCORE_PODS = 1024  # pods rescored per commit stop (nas_api.hip's window)
+RESCORE_PODS = 1024  # pods rescored per commit stop (csrc/pass_plan.h)
 
 
 def merge_lists(parts, K=_lib.K_CANDIDATES):

@@ -86,3 +86,24 @@ def test_asan_ubsan_launch_args(tmp_path):
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert "LAUNCH ARGS OK" in r.stdout
     assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr
+
+
+@pytest.mark.skipif(shutil.which("g++") is None or not os.path.isdir(HIP_INCLUDE),
+                    reason="needs g++ and the HIP headers")
+def test_asan_ubsan_pass_plan(tmp_path):
+    """Pass planning and result decoding (csrc/pass_plan.h, result_decode.h:
+    host-only headers) in a stand-alone program: the chunk plans DESIGN.md
+    quotes pinned offset by offset, cover / tile-alignment / termination over a
+    sweep of shapes, plan_pass()'s mode flags and note_pass() against the
+    expressions nas_place used to compute in line, and the decoders against
+    per-element restatements.  No GPU and no HIP runtime."""
+    exe = tmp_path / "pass_plan_driver"
+    subprocess.run(["g++", "-std=c++17", *SAN, "-D__HIP_PLATFORM_AMD__", "-I", HIP_INCLUDE,
+                    "-I", CSRC, os.path.join(ROOT, "tests", "sanitize", "pass_plan_driver.cpp"),
+                    "-o", str(exe)], check=True)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:halt_on_error=1",
+               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
+    r = subprocess.run([str(exe)], env=env, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert "PASS PLAN OK" in r.stdout
+    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr

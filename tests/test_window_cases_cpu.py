@@ -169,7 +169,7 @@ def _const(path, name):
 def test_source_constants_give_the_tested_boundaries():
     """A retuned constant moves a boundary: then the shapes of window_cases.py
     must move with it, or the GPU test stops reaching the launch form it names."""
-    wide_min = _const("nas_api.hip", "WIDE_MIN_PODS")
+    wide_min = _const("pass_plan.h", "WIDE_MIN_PODS")
     pad = _const("nas_internal.h", "WA_PAD_ROWS")
     stage = _const("nas_internal.h", "OVF_STAGE_ENTRIES")
     tile = _const("nas_internal.h", "COST_BN")

@@ -25,7 +25,7 @@ U64 = np.uint64
 # restated from the sources; test_window_cases_cpu.py pins them
 TILE = 256             # COST_BN: a window's cost launch is rounded to it
 WIDE_TILE = 384        # WIDE_PODS of k_cost.hip
-WIDE_MIN_PODS = 32768  # nas_api.hip: padded pods from which world 1 runs the wide tile
+WIDE_MIN_PODS = 32768  # csrc/pass_plan.h: padded pods from which world 1 runs the wide tile
 WA_PAD_ROWS = 256      # rows allocated behind the traffic
 OVF_STAGE_ENTRIES = 308
 
