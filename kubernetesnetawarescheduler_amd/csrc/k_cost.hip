@@ -34,7 +34,9 @@
 // per tile).
 #include "fit_wave.h"
 #include "klist.h"
+#include "traffic_ingest.h"
 
+#include <numeric>
 #include <type_traits>
 
 namespace nas {
@@ -1054,13 +1056,10 @@ hipError_t launch_cost_t(hipStream_t st, const void *Lt, const void *WA, int Mp,
 
 int cost_tile_pods(int) { return WIDE_PODS; }
 
-// wide tiles start at a launch's p0 (a multiple of BN) + 384 nt: multiples of 128
-int32_t ovf_window_max(const int32_t *ptr, int64_t rows) {
-    int32_t mx = 0;
-    for (int64_t s = 0; s < rows; s += 128)
-        mx = std::max(mx, ptr[std::min<int64_t>(s + WIDE_PODS, rows)] - ptr[s]);
-    return mx;
-}
+// wide tiles start at a launch's p0 (a multiple of BN) + WIDE_PODS nt: the
+// windows nas::ovf_window_max (traffic_ingest.h) takes Ovf::tile_max over
+static_assert(OVF_WINDOW_ROWS == WIDE_PODS, "ovf_window_max covers one wide tile");
+static_assert(OVF_WINDOW_STEP == std::gcd(BN, WIDE_PODS), "... from every row a wide tile starts at");
 
 // Kp: padded contraction length in ELEMENTS; np: pods, multiple of BN,
 // p0 + np <= Pp; Mp multiple of BM.

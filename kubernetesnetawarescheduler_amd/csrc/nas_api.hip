@@ -23,6 +23,7 @@
 #include "nas_internal.h"
 #include "pass_plan.h"
 #include "result_decode.h"
+#include "traffic_ingest.h"
 
 using nas::decode_cost;
 using nas::decode_int_score;
@@ -74,13 +75,41 @@ int ensure(nas_ctx *ctx, DevBuf &b, size_t bytes) {
     return NAS_OK;
 }
 
+// The temporary device buffers of one entry point.  The destructor leaves the
+// context's stream idle, then frees them, on every path out of the scope; so
+// declare it after the host vectors its copies read or write (they then
+// outlive every copy in flight on an early return).
+class Scratch {
+    nas_ctx *ctx_;
+    std::vector<void *> bufs_;
+
+  public:
+    explicit Scratch(nas_ctx *ctx) : ctx_(ctx) {}
+    Scratch(const Scratch &) = delete;
+    Scratch &operator=(const Scratch &) = delete;
+    ~Scratch() {
+        (void)hipStreamSynchronize(ctx_->stream);
+        for (void *p : bufs_) (void)hipFree(p);
+    }
+    template <typename T>
+    int alloc(T *&p, size_t bytes) {
+        DevBuf b;
+        const int rc = ensure(ctx_, b, bytes);
+        if (rc == NAS_OK) bufs_.push_back(b.p);
+        p = static_cast<T *>(b.p);
+        return rc;
+    }
+};
+
 }  // namespace nas
 
-#define HIPCK(expr)                                                  \
-    do {                                                             \
-        hipError_t e_ = (expr);                                      \
-        if (e_ != hipSuccess) return nas::hip_fail(ctx, e_, #expr);  \
+// (HIPCK_AS: the failure is reported under the call site's name for the step)
+#define HIPCK_AS(what, expr)                                        \
+    do {                                                            \
+        hipError_t e_ = (expr);                                     \
+        if (e_ != hipSuccess) return nas::hip_fail(ctx, e_, what);  \
     } while (0)
+#define HIPCK(expr) HIPCK_AS(#expr, expr)
 #define OK(expr)                   \
     do {                           \
         int r_ = (expr);           \
@@ -219,8 +248,8 @@ void set_geometry(nas_ctx *ctx, int n, int dtype) {
 
 // overflow lists of every pod row: ptr[B * Pp + 1] absolute offsets, entries
 // (node, excess); none -> ovf_n = 0 and the plane is the traffic
-int upload_ovf(nas_ctx *ctx, const std::vector<int32_t> &ptr, const std::vector<int32_t> &m,
-               const std::vector<int32_t> &e) {
+int upload_ovf(nas_ctx *ctx, const nas::OvfLists &ovf) {
+    const std::vector<int32_t> &ptr = ovf.ptr, &m = ovf.m, &e = ovf.e;
     ctx->ovf_n = (int64_t)m.size();
     if (m.empty()) return NAS_OK;
     ctx->ovf_tile_max = nas::ovf_window_max(ptr.data(), (int64_t)ptr.size() - 1);
@@ -231,6 +260,32 @@ int upload_ovf(nas_ctx *ctx, const std::vector<int32_t> &ptr, const std::vector<
     HIPCK(hipMemcpyAsync(ctx->ovf_m.p, m.data(), m.size() * 4, hipMemcpyHostToDevice, ctx->stream));
     HIPCK(hipMemcpyAsync(ctx->ovf_e.p, e.data(), e.size() * 4, hipMemcpyHostToDevice, ctx->stream));
     HIPCK(hipStreamSynchronize(ctx->stream));  // host vectors die with the caller
+    return NAS_OK;
+}
+
+// CSR aggregates (traffic_ingest.h) into the zeroed dense rows: the int8 plane
+// (k_plane_scatter) or the fp32 rows (k_scatter_f32)
+template <typename T>
+int scatter_triplets(nas_ctx *ctx, const nas::Triplets<T> &t) {
+    constexpr bool f32 = std::is_same<T, float>::value;
+    const char *what = f32 ? "csr f32 scatter" : "csr plane scatter";
+    const size_t k = t.pod.size();
+    nas::Scratch scratch(ctx);
+    int32_t *dp, *dn;
+    T *dv;
+    OK(scratch.alloc(dp, k * 4 + 4));
+    OK(scratch.alloc(dn, k * 4 + 4));
+    OK(scratch.alloc(dv, k * sizeof(T) + 4));
+    if (k == 0) return NAS_OK;
+    HIPCK_AS(what, hipMemcpyAsync(dp, t.pod.data(), k * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIPCK_AS(what, hipMemcpyAsync(dn, t.node.data(), k * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIPCK_AS(what, hipMemcpyAsync(dv, t.val.data(), k * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+    if constexpr (f32)
+        HIPCK_AS(what, nas::launch_scatter_f32(ctx->stream, dp, dn, dv, (int64_t)k, ctx->Kp,
+                                               ctx->WA.as<float>()));
+    else
+        HIPCK_AS(what, nas::launch_plane_scatter(ctx->stream, dp, dn, dv, (int64_t)k, ctx->Kp,
+                                                 ctx->WA.as<signed char>()));
     return NAS_OK;
 }
 
@@ -423,21 +478,6 @@ nas::CommitArgs commit_args(const nas_ctx *ctx, int p_begin, int p_end) {
     return {ctx->cand_key.as<uint64_t>(), ctx->cand_bound.as<uint64_t>(), ctx->req.as<int32_t>(),
             ctx->Pp, p_begin, p_end, ctx->cap.as<int32_t>(), ctx->N, ctx->out_node.as<int32_t>(),
             ctx->out_cost_i.as<int32_t>(), ctx->status.as<int32_t>(), zrow_ptr(ctx)};
-}
-
-// exact traffic row (n values, each within int32) -> the int8 plane row and
-// the row's overflow entries (node, excess)
-void split_row(const int64_t *v, int n, signed char *plane, std::vector<int32_t> &m,
-               std::vector<int32_t> &e) {
-    for (int j = 0; j < n; ++j) {
-        const int64_t x = v[j];
-        const int64_t c = x < -128 ? -128 : x > 127 ? 127 : x;
-        plane[j] = (signed char)c;
-        if (x != c) {
-            m.push_back(j);
-            e.push_back((int32_t)(x - c));
-        }
-    }
 }
 
 // the call issued collectives other ranks must join (waits get deadlines)
@@ -1760,19 +1800,18 @@ int nas_upload_latency(nas_ctx *ctx, const void *L, int32_t dtype, int32_t n) {
     const size_t e = esz(dtype);
     const size_t lt_b = (size_t)ctx->Mp * ctx->Kp * e;  // one cluster's Lt
     OK(nas::ensure(ctx, ctx->Lt, lt_b * ctx->B));
-    DevBuf tmp;
-    OK(nas::ensure(ctx, tmp, (size_t)n * n * e));
-    hipError_t he = hipSuccess;
-    for (int b = 0; b < ctx->B && he == hipSuccess; ++b) {
-        he = hipMemcpyAsync(tmp.p, static_cast<const char *>(L) + (size_t)b * n * n * e,
-                            (size_t)n * n * e, hipMemcpyHostToDevice, ctx->stream);
-        if (he == hipSuccess)
-            he = nas::launch_transpose_L(ctx->stream, tmp.p, dtype, n, ctx->Nloc0, ctx->Nloc,
-                                         ctx->Mp, ctx->Kp, ctx->Lt.as<char>() + b * lt_b);
+    nas::Scratch scratch(ctx);
+    void *tmp;
+    OK(scratch.alloc(tmp, (size_t)n * n * e));
+    for (int b = 0; b < ctx->B; ++b) {
+        HIPCK_AS("upload latency",
+                 hipMemcpyAsync(tmp, static_cast<const char *>(L) + (size_t)b * n * n * e,
+                                (size_t)n * n * e, hipMemcpyHostToDevice, ctx->stream));
+        HIPCK_AS("upload latency",
+                 nas::launch_transpose_L(ctx->stream, tmp, dtype, n, ctx->Nloc0, ctx->Nloc, ctx->Mp,
+                                         ctx->Kp, ctx->Lt.as<char>() + b * lt_b));
     }
-    if (he == hipSuccess) he = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(tmp.p);
-    if (he != hipSuccess) return nas::hip_fail(ctx, he, "upload latency");
+    HIPCK_AS("upload latency", hipStreamSynchronize(ctx->stream));
     ctx->have_L = true;
     ctx->L_n = n;
     ctx->L_dtype = dtype;
@@ -1964,7 +2003,8 @@ int nas_upload_traffic_dense(nas_ctx *ctx, const void *WA, int32_t dtype, int32_
         OK(traffic_common(ctx, NAS_DT_I8, P, n));
         const auto *src = static_cast<const int32_t *>(WA);
         const int B = ctx->B, Pp = ctx->Pp, Kp = ctx->Kp;
-        std::vector<int32_t> ptr((size_t)B * Pp + 1, 0), om, oe;
+        nas::OvfLists ovf;
+        ovf.ptr.assign((size_t)B * Pp + 1, 0);
         const int rows_blk = std::max(1, (int)std::min<int64_t>(P, (64 << 20) / std::max(1, n)));
         std::vector<signed char> plane((size_t)rows_blk * n);
         std::vector<int64_t> row(n);
@@ -1974,18 +2014,17 @@ int nas_upload_traffic_dense(nas_ctx *ctx, const void *WA, int32_t dtype, int32_
                 for (int i = 0; i < nr; ++i) {
                     const int32_t *r = src + ((size_t)b * P + p0 + i) * n;
                     for (int j = 0; j < n; ++j) row[j] = r[j];
-                    split_row(row.data(), n, plane.data() + (size_t)i * n, om, oe);
-                    ptr[(size_t)b * Pp + p0 + i + 1] = (int32_t)om.size();
+                    nas::split_row(row.data(), n, plane.data() + (size_t)i * n, ovf.m, ovf.e);
+                    ovf.ptr[(size_t)b * Pp + p0 + i + 1] = (int32_t)ovf.m.size();
                 }
                 HIPCK(hipMemcpy2DAsync(ctx->WA.as<char>() + ((size_t)b * Pp + p0) * Kp, (size_t)Kp,
                                        plane.data(), (size_t)n, (size_t)n, nr,
                                        hipMemcpyHostToDevice, ctx->stream));
                 HIPCK(hipStreamSynchronize(ctx->stream));  // plane is reused
             }
-        // padding rows carry the running offset
-        for (size_t r = 1; r < ptr.size(); ++r) ptr[r] = std::max(ptr[r], ptr[r - 1]);
-        if (om.size() > 0x7fffffffu) return nas::fail(ctx, NAS_ERR_UNSUPPORTED, "too many overflow entries");
-        OK(upload_ovf(ctx, ptr, om, oe));
+        nas::carry_offsets(ovf.ptr);
+        if (ovf.m.size() > 0x7fffffffu) return nas::fail(ctx, NAS_ERR_UNSUPPORTED, "too many overflow entries");
+        OK(upload_ovf(ctx, ovf));
         OK(finish_traffic_i8(ctx));
         ctx->have_wa = true;
         ctx->synth_valid = false;
@@ -2008,152 +2047,50 @@ int nas_upload_traffic_csr(nas_ctx *ctx, const int32_t *row_ptr, const int32_t *
                            const void *weight, int32_t dtype, int32_t P, int32_t n, int64_t nnz) {
     NAS_RANGE("nas_upload_traffic_csr");
     OK(bind(ctx));
-    if (!row_ptr || nnz < 0 || (nnz > 0 && (!peer_node || !weight)))
-        return nas::fail(ctx, NAS_ERR_ARG, "csr arrays");
-    if (dtype != NAS_DT_I8 && dtype != NAS_DT_I32 && dtype != NAS_DT_BF16 && dtype != NAS_DT_F32)
-        return nas::fail(ctx, NAS_ERR_ARG, "csr weight dtype");
+    std::string msg;
+    int rc = nas::check_csr_arrays(row_ptr, peer_node, weight, dtype, nnz, msg);
+    if (rc != NAS_OK) return nas::fail(ctx, rc, msg);
     if (ctx->B > 1) return nas::fail(ctx, NAS_ERR_UNSUPPORTED, "CSR traffic with a cluster batch");
-    if (P <= 0 || row_ptr[0] != 0 || row_ptr[P] != nnz)
-        return nas::fail(ctx, NAS_ERR_ARG, "row_ptr bounds");
-    for (int p = 0; p < P; ++p)
-        if (row_ptr[p + 1] < row_ptr[p]) return nas::fail(ctx, NAS_ERR_ARG, "row_ptr not monotone");
+    rc = nas::check_csr_rows(row_ptr, P, nnz, msg);
+    if (rc != NAS_OK) return nas::fail(ctx, rc, msg);
     if (dtype == NAS_DT_F32) {
         // fp32 traffic: per-node sums in fp64 on the host, rounded to fp32
         // once, scattered into the dense rows on the device
         OK(traffic_common(ctx, NAS_DT_F32, P, n));
-        std::vector<int32_t> tp, tn;
-        std::vector<float> tv;
-        std::vector<std::pair<int32_t, double>> agg;
-        const auto *wf = static_cast<const float *>(weight);
-        for (int p = 0; p < P; ++p) {
-            agg.clear();
-            for (int64_t x = row_ptr[p]; x < row_ptr[p + 1]; ++x)
-                if (peer_node[x] >= 0 && peer_node[x] < n) agg.push_back({peer_node[x], (double)wf[x]});
-            std::sort(agg.begin(), agg.end(),
-                      [](const auto &a, const auto &b) { return a.first < b.first; });
-            for (size_t i = 0; i < agg.size();) {
-                const int32_t m = agg[i].first;
-                double v = 0;
-                for (; i < agg.size() && agg[i].first == m; ++i) v += agg[i].second;
-                tp.push_back(p);
-                tn.push_back(m);
-                tv.push_back((float)v);
-            }
-        }
-        DevBuf dp, dn, dv;
-        int rc = nas::ensure(ctx, dp, tp.size() * 4 + 4);
-        if (rc == NAS_OK) rc = nas::ensure(ctx, dn, tn.size() * 4 + 4);
-        if (rc == NAS_OK) rc = nas::ensure(ctx, dv, tv.size() * 4 + 4);
-        hipError_t he = hipSuccess;
-        if (rc == NAS_OK && !tp.empty()) {
-            he = hipMemcpyAsync(dp.p, tp.data(), tp.size() * 4, hipMemcpyHostToDevice, ctx->stream);
-            if (he == hipSuccess)
-                he = hipMemcpyAsync(dn.p, tn.data(), tn.size() * 4, hipMemcpyHostToDevice, ctx->stream);
-            if (he == hipSuccess)
-                he = hipMemcpyAsync(dv.p, tv.data(), tv.size() * 4, hipMemcpyHostToDevice, ctx->stream);
-            if (he == hipSuccess)
-                he = nas::launch_scatter_f32(ctx->stream, dp.as<int32_t>(), dn.as<int32_t>(),
-                                             dv.as<float>(), (int64_t)tp.size(), ctx->Kp,
-                                             ctx->WA.as<float>());
-        }
-        (void)hipStreamSynchronize(ctx->stream);
-        for (DevBuf *b : {&dp, &dn, &dv})
-            if (b->p) (void)hipFree(b->p);
-        if (rc != NAS_OK) return rc;
-        if (he != hipSuccess) return nas::hip_fail(ctx, he, "csr f32 scatter");
-        ctx->have_wa = true;
-        ctx->synth_valid = false;
-        return NAS_OK;
-    }
-    if (dtype != NAS_DT_BF16) {
+        nas::Triplets<float> t;
+        nas::ingest_csr_f32(row_ptr, peer_node, static_cast<const float *>(weight), P, n, t);
+        OK(scatter_triplets(ctx, t));
+    } else if (dtype != NAS_DT_BF16) {
         // exact integer aggregation on the host (int64 sums, then int32 range):
         // the plane entries are scattered on the device, the rest is overflow
         OK(traffic_common(ctx, NAS_DT_I8, P, n));
-        std::vector<int32_t> ptr((size_t)ctx->Pp + 1, 0), om, oe, tp, tn;
-        std::vector<signed char> tv;
-        std::vector<std::pair<int32_t, int64_t>> agg;
-        for (int p = 0; p < P; ++p) {
-            agg.clear();
-            for (int64_t x = row_ptr[p]; x < row_ptr[p + 1]; ++x) {
-                const int32_t m = peer_node[x];
-                if (m < 0 || m >= n) continue;  // unbound peer (or off-cluster): skipped
-                const int64_t w = dtype == NAS_DT_I8 ? (int64_t) static_cast<const int8_t *>(weight)[x]
-                                                     : (int64_t) static_cast<const int32_t *>(weight)[x];
-                agg.push_back({m, w});
-            }
-            std::sort(agg.begin(), agg.end(),
-                      [](const auto &a, const auto &b) { return a.first < b.first; });
-            for (size_t i = 0; i < agg.size();) {
-                const int32_t m = agg[i].first;
-                int64_t v = 0;
-                for (; i < agg.size() && agg[i].first == m; ++i) v += agg[i].second;
-                if (v < INT32_MIN || v > INT32_MAX)
-                    return nas::fail(ctx, NAS_ERR_UNSUPPORTED,
-                                     "traffic of pod " + std::to_string(p) + " to node " +
-                                         std::to_string(m) + " exceeds int32");
-                if (v == 0) continue;
-                const int64_t c = v < -128 ? -128 : v > 127 ? 127 : v;
-                tp.push_back(p);
-                tn.push_back(m);
-                tv.push_back((signed char)c);
-                if (v != c) {
-                    om.push_back(m);
-                    oe.push_back((int32_t)(v - c));
-                }
-            }
-            ptr[p + 1] = (int32_t)om.size();
-        }
-        for (size_t r = (size_t)P + 1; r < ptr.size(); ++r) ptr[r] = ptr[r - 1];
-        DevBuf dp, dn, dv;
-        int rc = nas::ensure(ctx, dp, tp.size() * 4 + 4);
-        if (rc == NAS_OK) rc = nas::ensure(ctx, dn, tn.size() * 4 + 4);
-        if (rc == NAS_OK) rc = nas::ensure(ctx, dv, tv.size() + 4);
-        hipError_t he = hipSuccess;
-        if (rc == NAS_OK && !tp.empty()) {
-            he = hipMemcpyAsync(dp.p, tp.data(), tp.size() * 4, hipMemcpyHostToDevice, ctx->stream);
-            if (he == hipSuccess)
-                he = hipMemcpyAsync(dn.p, tn.data(), tn.size() * 4, hipMemcpyHostToDevice, ctx->stream);
-            if (he == hipSuccess)
-                he = hipMemcpyAsync(dv.p, tv.data(), tv.size(), hipMemcpyHostToDevice, ctx->stream);
-            if (he == hipSuccess)
-                he = nas::launch_plane_scatter(ctx->stream, dp.as<int32_t>(), dn.as<int32_t>(),
-                                               dv.as<signed char>(), (int64_t)tp.size(), ctx->Kp,
-                                               ctx->WA.as<signed char>());
-        }
-        (void)hipStreamSynchronize(ctx->stream);
-        for (DevBuf *b : {&dp, &dn, &dv})
-            if (b->p) (void)hipFree(b->p);
-        if (rc != NAS_OK) return rc;
-        if (he != hipSuccess) return nas::hip_fail(ctx, he, "csr plane scatter");
-        OK(upload_ovf(ctx, ptr, om, oe));
+        nas::Triplets<signed char> t;
+        nas::OvfLists ovf;
+        rc = nas::ingest_csr_int(row_ptr, peer_node, weight, dtype, P, ctx->Pp, n, t, ovf, msg);
+        if (rc != NAS_OK) return nas::fail(ctx, rc, msg);
+        OK(scatter_triplets(ctx, t));
+        OK(upload_ovf(ctx, ovf));
         OK(finish_traffic_i8(ctx));
-        ctx->have_wa = true;
-        ctx->synth_valid = false;
-        return NAS_OK;
+    } else {
+        OK(traffic_common(ctx, dtype, P, n));
+        nas::Scratch scratch(ctx);
+        int32_t *rp, *pn;
+        uint16_t *w;
+        OK(scratch.alloc(rp, (size_t)(P + 1) * 4));
+        OK(scratch.alloc(pn, (size_t)nnz * 4));
+        OK(scratch.alloc(w, (size_t)nnz * 2));
+        HIPCK_AS("csr aggregate", hipMemcpyAsync(rp, row_ptr, (size_t)(P + 1) * 4,
+                                                 hipMemcpyHostToDevice, ctx->stream));
+        if (nnz) {
+            HIPCK_AS("csr aggregate", hipMemcpyAsync(pn, peer_node, (size_t)nnz * 4,
+                                                     hipMemcpyHostToDevice, ctx->stream));
+            HIPCK_AS("csr aggregate", hipMemcpyAsync(w, weight, (size_t)nnz * 2,
+                                                     hipMemcpyHostToDevice, ctx->stream));
+        }
+        HIPCK_AS("csr aggregate", nas::launch_csr_aggregate_bf16(ctx->stream, rp, pn, w, P, n, ctx->Kp,
+                                                                 ctx->WA.as<uint16_t>()));
+        HIPCK_AS("csr aggregate", hipStreamSynchronize(ctx->stream));
     }
-    OK(traffic_common(ctx, dtype, P, n));
-    DevBuf rp, pn, w;
-    int rc = nas::ensure(ctx, rp, (size_t)(P + 1) * 4);
-    if (rc == NAS_OK) rc = nas::ensure(ctx, pn, (size_t)nnz * 4);
-    if (rc == NAS_OK) rc = nas::ensure(ctx, w, (size_t)nnz * 2);
-    hipError_t he = hipSuccess;
-    if (rc == NAS_OK) {
-        he = hipMemcpyAsync(rp.p, row_ptr, (size_t)(P + 1) * 4, hipMemcpyHostToDevice, ctx->stream);
-        if (he == hipSuccess && nnz)
-            he = hipMemcpyAsync(pn.p, peer_node, (size_t)nnz * 4, hipMemcpyHostToDevice, ctx->stream);
-        if (he == hipSuccess && nnz)
-            he = hipMemcpyAsync(w.p, weight, (size_t)nnz * 2, hipMemcpyHostToDevice, ctx->stream);
-        if (he == hipSuccess)
-            he = nas::launch_csr_aggregate_bf16(ctx->stream, rp.as<int32_t>(), pn.as<int32_t>(),
-                                                w.as<uint16_t>(), P, n, ctx->Kp,
-                                                ctx->WA.as<uint16_t>());
-        if (he == hipSuccess) he = hipStreamSynchronize(ctx->stream);
-    }
-    (void)hipStreamSynchronize(ctx->stream);
-    for (DevBuf *b : {&rp, &pn, &w})
-        if (b->p) (void)hipFree(b->p);
-    if (rc != NAS_OK) return rc;
-    if (he != hipSuccess) return nas::hip_fail(ctx, he, "csr aggregate");
     ctx->have_wa = true;
     ctx->synth_valid = false;
     return NAS_OK;
@@ -3446,19 +3383,21 @@ static int synth(nas_ctx *ctx, uint64_t seed, int32_t B, int32_t n_nodes, int32_
         // exact traffic: peer aggregates beyond the int8 plane go to the
         // overflow lists (counts, host prefix sum, entries)
         const size_t rows = (size_t)B * ctx->Pp;
-        DevBuf cnt;
-        OK(nas::ensure(ctx, cnt, rows * 4));
-        hipError_t he = hipMemsetAsync(cnt.p, 0, rows * 4, ctx->stream);
-        for (int b = 0; b < B && he == hipSuccess; ++b)
-            he = nas::launch_synth_overflow(ctx->stream, seed + b, n_nodes, P, ovf_peers, ctx->Kp, 0,
-                                            nullptr, cnt.as<int32_t>() + (size_t)b * ctx->Pp,
-                                            nullptr, nullptr, nullptr);
         std::vector<int32_t> c(rows), ptr(rows + 1, 0);
-        if (he == hipSuccess)
-            he = hipMemcpyAsync(c.data(), cnt.p, rows * 4, hipMemcpyDeviceToHost, ctx->stream);
-        if (he == hipSuccess) he = hipStreamSynchronize(ctx->stream);
-        (void)hipFree(cnt.p);
-        if (he != hipSuccess) return nas::hip_fail(ctx, he, "synth overflow counts");
+        {
+            const char *what = "synth overflow counts";
+            nas::Scratch scratch(ctx);
+            int32_t *cnt;
+            OK(scratch.alloc(cnt, rows * 4));
+            HIPCK_AS(what, hipMemsetAsync(cnt, 0, rows * 4, ctx->stream));
+            for (int b = 0; b < B; ++b)
+                HIPCK_AS(what, nas::launch_synth_overflow(ctx->stream, seed + b, n_nodes, P, ovf_peers,
+                                                          ctx->Kp, 0, nullptr,
+                                                          cnt + (size_t)b * ctx->Pp, nullptr, nullptr,
+                                                          nullptr));
+            HIPCK_AS(what, hipMemcpyAsync(c.data(), cnt, rows * 4, hipMemcpyDeviceToHost, ctx->stream));
+            HIPCK_AS(what, hipStreamSynchronize(ctx->stream));
+        }
         int64_t tot = 0;
         for (size_t r = 0; r < rows; ++r) {
             tot += c[r];
@@ -3543,27 +3482,21 @@ int nas_read_inputs(nas_ctx *ctx, int32_t p0, int32_t np, void *WA_rows, void *L
                 }
             }
             HIPCK(hipStreamSynchronize(ctx->stream));
-            auto *out = static_cast<int32_t *>(WA_rows);
-            for (size_t i = 0; i < pl.size(); ++i) out[i] = pl[i];
-            if (ctx->ovf_n)
-                for (int r = 0; r < np; ++r)
-                    for (int j = ptr[r]; j < ptr[r + 1]; ++j)
-                        out[(size_t)r * N + om[j - ptr[0]]] += oe[j - ptr[0]];
+            nas::join_rows(pl.data(), np, N, ptr.data(), om.data(), oe.data(),
+                           static_cast<int32_t *>(WA_rows));
         }
     }
     if (L) {
         if (ctx->synth_valid) {
-            DevBuf tmp;
-            OK(nas::ensure(ctx, tmp, (size_t)N * N * e));
-            hipError_t he = nas::launch_synth_cluster(ctx->stream, ctx->synth_seed, N, ctx->P,
-                                                      ctx->dtype, 1, 0, 0, 0, 0, 0, nullptr,
-                                                      nullptr, nullptr, nullptr, tmp.p,
-                                                      ctx->synth_profile);
-            if (he == hipSuccess)
-                he = hipMemcpyAsync(L, tmp.p, (size_t)N * N * e, hipMemcpyDeviceToHost, ctx->stream);
-            if (he == hipSuccess) he = hipStreamSynchronize(ctx->stream);
-            (void)hipFree(tmp.p);
-            if (he != hipSuccess) return nas::hip_fail(ctx, he, "read L");
+            nas::Scratch scratch(ctx);
+            void *tmp;
+            OK(scratch.alloc(tmp, (size_t)N * N * e));
+            HIPCK_AS("read L", nas::launch_synth_cluster(ctx->stream, ctx->synth_seed, N, ctx->P,
+                                                         ctx->dtype, 1, 0, 0, 0, 0, 0, nullptr, nullptr,
+                                                         nullptr, nullptr, tmp, ctx->synth_profile));
+            HIPCK_AS("read L", hipMemcpyAsync(L, tmp, (size_t)N * N * e, hipMemcpyDeviceToHost,
+                                              ctx->stream));
+            HIPCK_AS("read L", hipStreamSynchronize(ctx->stream));
         } else if (ctx->world == 1) {
             std::vector<char> lt((size_t)N * ctx->Kp * e);
             HIPCK(hipMemcpyAsync(lt.data(), ctx->Lt.p, lt.size(), hipMemcpyDeviceToHost, ctx->stream));

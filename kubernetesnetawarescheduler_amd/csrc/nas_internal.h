@@ -96,11 +96,9 @@ struct Ovf {
     const int32_t *row_count = nullptr;
     int N = 0;  // rows of one cluster's Lr
     // most entries of any 384 consecutive rows from a multiple of 128 (where
-    // wide tiles start): ovf_window_max over ptr
+    // wide tiles start): ovf_window_max (traffic_ingest.h) over ptr
     int tile_max = 0x7fffffff;
 };
-// (host) that maximum for ptr[0 .. rows]
-int32_t ovf_window_max(const int32_t *ptr, int64_t rows);
 
 // In-process transport (nas_comm_init_local): G contexts of one process, each
 // driven by its own host thread, exchange candidate lists through device

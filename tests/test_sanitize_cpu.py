@@ -107,3 +107,23 @@ def test_asan_ubsan_pass_plan(tmp_path):
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert "PASS PLAN OK" in r.stdout
     assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_asan_ubsan_traffic_ingest(tmp_path):
+    """Traffic ingestion (csrc/traffic_ingest.h: a host-only header) in a
+    stand-alone program: CSR aggregation into plane triplets and overflow
+    lists, the clamp / excess rule and its inverse, the offset fix-up, the
+    argument checks and ovf_window_max, on literal pins at the int8 and int32
+    limits and over random small cases against a dense restatement.  No GPU
+    and no HIP runtime."""
+    exe = tmp_path / "traffic_ingest_driver"
+    subprocess.run(["g++", "-std=c++17", *SAN, "-I", CSRC,
+                    os.path.join(ROOT, "tests", "sanitize", "traffic_ingest_driver.cpp"),
+                    "-o", str(exe)], check=True)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:halt_on_error=1",
+               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
+    r = subprocess.run([str(exe)], env=env, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert "TRAFFIC INGEST OK" in r.stdout
+    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr
